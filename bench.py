@@ -15,11 +15,15 @@ One timed step, on every rank:
      late; ``--gather rccl``: an RCCL gather of a packed device row) -> push into the
      LIFO result hub.
 
-After the timed region, rank 0 serves the hub over gRPC on loopback and a client
-subprocess measures GetSegmentedObjects latency while all ranks keep stepping
-(the RPC is served under inference load, as in production).
+A plain run sets up, warms up, times the K steps and prints one JSON line (frames/s,
+``ms_per_step``). ``--dump-outputs DIR`` also writes what the last timed step computed
+(``DIR/records.npy``, ``DIR/labels.npy``; the inputs are seeded, so two builds can be
+compared output for output). With ``--full``, after the timed region rank 0 serves the hub
+over gRPC on loopback and a client subprocess measures GetSegmentedObjects latency while
+all ranks keep stepping (the RPC is served under inference load, as in production); a
+plain run reports the two latency fields as null.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 
 ``--gpus N`` means N ranks in both launch forms: under torchrun it must equal WORLD_SIZE
@@ -82,7 +86,16 @@ def main() -> int:
                         "RCCL data path is in use (--ingest scatter, the RCCL gather), else gloo")
     p.add_argument("--contour_mode", choices=["fast", "exact", "none"], default="fast")
     p.add_argument("--no-graph", dest="graph", action="store_false")
-    p.add_argument("--rpc", type=int, default=2000, help="GetSegmentedObjects calls to time (0: skip)")
+    p.add_argument("--rpc", type=int, default=2000,
+                   help="with --full: GetSegmentedObjects calls to time (0: skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the "
+                        "GetSegmentedObjects latency under inference load (--rpc calls)")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs to DIR: "
+                        "records.npy (float64 rows: label, score, area, cx, cy, stream, frame; "
+                        "rank 0, every rank's records) and labels.npy (float32, this rank's label "
+                        "maps; a fixed seeded sample of them above 48 MB)")
     p.add_argument("--dtype", default="bf16")
     p.add_argument("--streams", type=int, default=1,
                    help="concurrent camera streams per GPU: their frames fill one batched step "
@@ -103,6 +116,10 @@ def main() -> int:
     a = p.parse_args()
     if a.gpus < 1:
         p.error("--gpus must be >= 1")
+    if not a.full:
+        a.rpc = 0  # the RPC latency takes a run of its own after the timed steps
+    if a.serve and a.dump_outputs:
+        p.error("--dump-outputs writes the bench loop's outputs; --serve does not run it")
     if not a.supervise:
         ws = os.environ.get("WORLD_SIZE")
         if ws is not None and int(ws) != a.gpus:
@@ -187,6 +204,20 @@ def main() -> int:
     verbose = os.environ.get("SSA_BENCH_VERBOSE", "0") == "1"
 
     staged = [False]  # the first batch of a run is already on its way (steady state)
+    # --dump-outputs: what the last step handed back -- its records are in what the last
+    # step() (lag 0) or the flush() after it (lag >= 1) returns -- and its label maps
+    kept = None
+    last_dev = {}
+    if a.dump_outputs:
+        from collections import deque
+        kept = deque(maxlen=2)
+        run_device = engine.run_device
+
+        def _run_device(frames):
+            out = run_device(frames)
+            last_dev["labels"] = out[0]
+            return out
+        engine.run_device = _run_device
 
     def run_steps(n: int, k0: int = 0, stage_next: bool = True) -> None:
         # double-buffered ingest: the next batch's H2D overlaps this step's compute;
@@ -197,10 +228,14 @@ def main() -> int:
             pipe.prefetch(host_batches[k0 % 2])
         for k in range(n):
             last = k + 1 == n
-            pipe.step(next_frames=host_batches[(k0 + k + 1) % 2] if (not last or stage_next) else None)
+            recs = pipe.step(next_frames=host_batches[(k0 + k + 1) % 2] if (not last or stage_next) else None)
+            if kept is not None:
+                kept.append(recs)
             if verbose:
                 print(f"[rank {ctx.rank}] step {k0 + k} ok", file=sys.stderr, flush=True)
-        pipe.flush()
+        recs = pipe.flush()
+        if kept is not None:
+            kept.append(recs)
         staged[0] = stage_next
 
     sync = (lambda: torch.cuda.synchronize(ctx.device)) if ctx.device.type == "cuda" else (lambda: None)
@@ -240,6 +275,9 @@ def main() -> int:
     streams_seen = sorted(int(k) for k in pipe.stream_frames)
     frames_collected = int(sum(pipe.stream_frames.values()))
     order_errors = int(pipe.frame_order_errors)
+
+    if a.dump_outputs and ctx.is_root:
+        _dump_outputs(a.dump_outputs, ctx, pipe, kept, last_dev.get("labels"))
 
     rpc = None
     if a.rpc > 0:
@@ -302,6 +340,37 @@ def main() -> int:
     pipe.close()  # the pipeline's RCCL communicators, before the process group
     D.destroy(ctx)
     return 0
+
+
+DUMP_LABEL_BYTES = 48 << 20  # of the 64 MB a dump may take; the records are a few KB
+
+
+def _dump_outputs(path: str, ctx, pipe, kept, labels) -> None:
+    """Rank 0, after the timed steps: the last timed step's outputs as .npy files.
+
+    ``records.npy``: the records the pipeline returned for the last step's frames (every
+    rank's), one float64 row (label, score, area, cx, cy, stream, frame) each, in the order
+    returned; the capture timestamp, a wall-clock time, is left out. ``labels.npy``: the
+    label maps those records were computed from on this rank, float32; above
+    DUMP_LABEL_BYTES the flat elements at a fixed seeded sample of indices."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    # the frame ids of the last step (DataParallelPipeline._step's running counters)
+    prev = pipe.frames_done - pipe.B * ctx.world
+    node_ids = pipe.ingest == "scatter" and ctx.initialized and ctx.world > 1
+    first = prev if node_ids else prev // ctx.world
+    cols = ("label", "score", "area", "cx", "cy", "stream", "frame")
+    recs = [r[r["frame"] >= first] for r in (kept or []) if len(r)]
+    rows = [np.stack([r[c].astype(np.float64) for c in cols], 1) for r in recs]
+    np.save(os.path.join(path, "records.npy"),
+            np.concatenate(rows) if rows else np.zeros((0, len(cols)), np.float64))
+    if labels is not None:
+        lab = np.ascontiguousarray(labels.detach().cpu().numpy()).astype(np.float32)
+        cap = DUMP_LABEL_BYTES // 4
+        if lab.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(lab.size, cap, replace=False))
+            lab = lab.reshape(-1)[idx]
+        np.save(os.path.join(path, "labels.npy"), lab)
 
 
 def _free_port() -> int:

@@ -7,7 +7,7 @@
 #   tests        pytest -m gpu (whole suite, one process)
 #   tests:EXPR   pytest -m gpu -k EXPR
 #   smoke        __graft_entry__.smoke()
-#   bench        driver window x2 (python bench.py --steps 20 --warmup 5)
+#   bench        driver window x2 (python bench.py --steps 20 --warmup 5 --full: RPC under load)
 #   bench100     100 timed steps, RPC under load
 #   b1           batch-1 bench (400 steps)
 #   b1lat        batch-1 bench at lag 0 (each step's records collected in the step: latency mode)
@@ -78,8 +78,8 @@ for step in "$@"; do
                -k "${step#tests:}" > $O/pytest_k.txt 2>&1 || { tail -30 $O/pytest_k.txt; exit 1; }; tail -5 $O/pytest_k.txt ;;
     smoke)   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 \
                || { tail -20 $O/smoke.txt; exit 1; }; tail -3 $O/smoke.txt ;;
-    bench)   bench d1 300 --steps 20 --warmup 5 && bench d2 300 --steps 20 --warmup 5 || exit 2 ;;
-    bench100) bench s100 300 --steps 100 --warmup 10 || exit 2 ;;
+    bench)   bench d1 300 --steps 20 --warmup 5 --full && bench d2 300 --steps 20 --warmup 5 --full || exit 2 ;;
+    bench100) bench s100 300 --steps 100 --warmup 10 --full || exit 2 ;;
     b1)      bench b1 300 --batch 1 --steps 400 --warmup 50 --rpc 0 || exit 2 ;;
     b1lat)   bench b1lat 300 --batch 1 --lag 0 --steps 400 --warmup 50 --rpc 0 || exit 2 ;;
     b1lag1)  bench b1lag1 300 --batch 1 --lag 1 --steps 400 --warmup 50 --rpc 0 || exit 2 ;;
@@ -112,7 +112,7 @@ for step in "$@"; do
     race)    timeout -k 10 600 python scripts/debug_race.py $RACE_ARGS > $O/race.txt 2>&1 || { tail -20 $O/race.txt; exit 5; }; tail -5 $O/race.txt ;;
     share8|share:*) n=${step#share}; n=${n#:}
              SSA_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-               --master-addr 127.0.0.1 --master-port 29581 bench.py --gpus $n --steps 10 --warmup 3 --rpc 300 $BENCH_ARGS \
+               --master-addr 127.0.0.1 --master-port 29581 bench.py --gpus $n --steps 10 --warmup 3 --full --rpc 300 $BENCH_ARGS \
                > $O/share$n.json 2> $O/share$n.err || { grep -v "^\[Gloo\]" $O/share$n.err | tail -30; exit 5; }
              cut -c1-600 $O/share$n.json ;;
     postab)  for m in 0 1 2; do SSA_POST_ACCUM=$m timeout -k 10 120 tools/bin/post_bench 50 > $O/post_accum$m.txt 2>&1 \

@@ -16,7 +16,8 @@ from semantic_segmentation_server_amd.api import service as S
 from semantic_segmentation_server_amd.labels import load_labels
 from semantic_segmentation_server_amd.runtime.results import RECORD_DTYPE, ResultBuffer, ResultHub, make_records
 
-REF_PB2 = "/root/reference/sem_seg_server_pb2.py"
+REF_DESCRIPTOR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                              "sem_seg_server_v1_descriptor.json")
 
 
 def _f32(tag, v):
@@ -51,21 +52,15 @@ def test_service_names():
         "sem_seg_server.SegmentedObjectData"
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PB2), reason="reference not mounted")
 def test_descriptor_matches_reference_serialized_descriptor():
-    """Parse the reference's embedded FileDescriptorProto bytes (without executing
-    its module) and compare every message/field/method."""
-    import ast
-    from google.protobuf import descriptor_pb2
-    tree = ast.parse(open(REF_PB2).read())
-    blob = None
-    for node in ast.walk(tree):
-        if isinstance(node, ast.keyword) and node.arg == "serialized_pb":
-            blob = ast.literal_eval(node.value)
-    assert blob is not None
-    ref = descriptor_pb2.FileDescriptorProto.FromString(blob)
+    """Compare every message/field/method with the reference's FileDescriptorProto, as
+    recorded in tests/golden (package; per message the sorted (name, number, type, label,
+    type_name) of its fields; per method (name, input type, output type))."""
+    import json
+    with open(REF_DESCRIPTOR) as f:
+        ref = json.load(f)
     ours = P.v1_file_descriptor()
-    assert ref.package == ours.package
+    assert ref["package"] == ours.package
 
     def msgs(fd):
         out = {}
@@ -77,10 +72,11 @@ def test_descriptor_matches_reference_serialized_descriptor():
         for m in fd.message_type:
             walk(m, "")
         return out
-    assert msgs(ref) == msgs(ours)
-    rs = {(m.name, m.input_type, m.output_type) for s in ref.service for m in s.method}
+    assert len(ref["messages"]) == 5
+    assert {k: [tuple(f) for f in v] for k, v in ref["messages"].items()} == msgs(ours)
+    rs = {tuple(m) for m in ref["methods"]}
     os_ = {(m.name, m.input_type, m.output_type) for s in ours.service for m in s.method}
-    assert rs == os_
+    assert len(rs) == 2 and rs == os_
 
 
 def _recs(labels):

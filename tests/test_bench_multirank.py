@@ -82,6 +82,89 @@ def test_bench_gpus_without_launcher_cpu():
     assert out["pg_backend"] == "gloo" and out["gather"] == "host" and out["rccl_nranks"] is None
 
 
+def test_bench_dump_outputs_and_full_cpu(tmp_path):
+    """A plain run times its steps and leaves the RPC latency out; ``--full`` measures it.
+    ``--dump-outputs`` writes the last timed step's records and label maps as float .npy
+    files, the same from run to run (seeded inputs and weights)."""
+    import numpy as np
+    steps, warmup, batch = 3, 1, 2
+    env = dict(os.environ, OMP_NUM_THREADS="1", SSA_NUMA_PIN="0", CUDA_VISIBLE_DEVICES="",
+               HIP_VISIBLE_DEVICES="")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    outs = []
+    for tag, extra in (("plain", []), ("full", ["--full", "--rpc", "20"])):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+               "--warmup", str(warmup), "--backend", "torch", "--input_size", "129",
+               "--batch", str(batch), "--dump-outputs", str(d)] + extra
+        r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == steps and out["ms_per_step"] > 0 and out["value"] > 0
+        assert sorted(p.name for p in d.iterdir()) == ["labels.npy", "records.npy"]
+        rec, lab = np.load(d / "records.npy"), np.load(d / "labels.npy")
+        assert rec.dtype == np.float64 and rec.ndim == 2 and rec.shape[1] == 7
+        assert lab.dtype == np.float32 and lab.shape[0] == batch
+        assert 0 <= lab.min() and lab.max() <= 20
+        # only the last timed step's frames (running ids: warmup + steps steps of `batch`)
+        assert (rec[:, 6] >= (warmup + steps - 1) * batch).all()
+        outs.append((out, rec, lab))
+    (plain, rec0, lab0), (full, rec1, lab1) = outs
+    assert plain["p50_get_segmented_objects_ms"] is None
+    assert full["p50_get_segmented_objects_ms"] is not None and full["p50_get_segmented_objects_ms"] > 0
+    assert np.array_equal(rec0, rec1) and np.array_equal(lab0, lab1)
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_steps():
+    """On the HIP path (three plan copies in flight, records collected two steps late) the
+    dumped label maps and records are those of the LAST timed step: the same frames (the
+    bench's seeded source; step k reads host batch k % 2) through an engine of this process
+    give the same label maps bit for bit (the graph path is bit-exact against itself,
+    smoke()) and the same records. Record floats: ratios of per-segment sums over at most
+    513^2 pixels in float32, so two summation orders differ by far less than 1e-5
+    relative."""
+    import tempfile
+    import numpy as np
+    import torch
+    from semantic_segmentation_server_amd import config as C
+    from semantic_segmentation_server_amd.runtime.engine import Engine
+    from semantic_segmentation_server_amd.runtime.sources import SyntheticSource
+    steps, warmup, batch = 5, 2, 4
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    with tempfile.TemporaryDirectory() as d:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", str(warmup), "--batch", str(batch), "--dump-outputs", d],
+                           cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                           timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        lab, rec = np.load(os.path.join(d, "labels.npy")), np.load(os.path.join(d, "records.npy"))
+    assert out["steps"] == steps and out["p50_get_segmented_objects_ms"] is None
+    assert lab.dtype == np.float32 and rec.dtype == np.float64
+    src = SyntheticSource(640, 480, stream=0, seed=1, pool=max(2, min(batch, 8)))
+    host = [src.read_batch(batch)[0] for _ in range(2)]
+    last = warmup + steps - 1
+    ids = list(range(last * batch, (last + 1) * batch))
+    eng = Engine(C.Config(backend="hip", batch=batch, input_size=513, graph=True), torch.device("cuda", 0))
+    want = eng.step(host[last % 2], ids, [0.0] * batch, 0)
+    torch.cuda.synchronize()
+    want_lab = eng._static["labels"].cpu().numpy()
+    assert lab.shape == want_lab.shape and np.array_equal(lab, want_lab.astype(np.float32))
+    assert len(want) >= 1 and len(rec) == len(want)
+    for j, c in enumerate(("label", "score", "area", "cx", "cy", "stream", "frame")):
+        if c in ("label", "stream", "frame"):
+            assert np.array_equal(rec[:, j], want[c].astype(np.float64)), c
+        else:
+            np.testing.assert_allclose(rec[:, j], want[c].astype(np.float64), rtol=1e-5, atol=0, err_msg=c)
+
+
 def test_bench_world_size_mismatch_fails():
     """Under a launcher, --gpus must match WORLD_SIZE: a silent 1-rank run is an error."""
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", CUDA_VISIBLE_DEVICES="",

@@ -1,7 +1,7 @@
 """Native V4L2 capture (csrc/host/v4l2.cpp): the YUYV/UYVY -> BGR conversion against
 the float BT.601 limited-range formula, and the capture path's failure modes on a
 machine without a camera. Parity with OpenCV's own conversion is unpinned (cv2 is
-not importable); the reference reads its camera at /root/reference/sem_seg_server.py:144-148."""
+not importable); the reference reads its camera in its sem_seg_server.py:144-148."""
 import os
 
 import numpy as np
