@@ -29,6 +29,8 @@ def test_cpulist_parse():
 
 def test_pin_to_gpu_numa(tmp_path, monkeypatch):
     root = str(tmp_path)
+    for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES"):  # a device mask of the host's is not the tree's
+        monkeypatch.delenv(var, raising=False)
     cpus, half = _tree(root, [(0x11, 0), (0x91, 1)])
     assert A.gpu_pci_addresses(root) == ["0000:11:00.0", "0000:91:00.0"]
     assert A.gpu_numa_node(1, root) == 1

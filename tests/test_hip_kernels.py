@@ -344,14 +344,18 @@ def test_stem_fused_preprocess(cam, k, cout):
         torch.cuda.synchronize()
         assert torch.isfinite(o2.float()).all()
         assert _rel(_nchw(o2).cpu(), ref) < 2e-2, tile
-    exp = torch.clamp(torch.round(ref / 0.05), -127, 127)
+    # int8 output against the conv of bf16-rounded operands in float64 (pixels normalised with
+    # one rounding, as the kernels' fused multiply-add does): at most one step off, <= 1e-3
+    import int8_ref as I
+    xk = I.letterbox_pixels(frames, torch.tensor(lx.tolist()), torch.tensor(ly.tolist()), I.stem_pixel_table())
+    exp = I.requant(torch.clamp(I.stem_ref_values(xk, w, b, 2, bf16_operands=True), 0.0, 6.0), 0.05)
     for tile, pw in [((8, 16), False)] + ([((32, 32), True)] if (k, cout) == (7, 64) else []):
         o8 = torch.empty(2, OH, OW, cout, dtype=torch.int8, device=DEV)
         K.stem_mfma(frames.to(DEV), torch.tensor(lx, device=DEV), torch.tensor(ly, device=DEV), wpk,
                     b.to(DEV), o8, H=H, W=W, OH=OH, OW=OW, Cout=cout, k=k, stride=2, act="relu6",
                     out_scale=0.05, tile=tile, per_wave=pw)
         torch.cuda.synchronize()
-        assert (_nchw(o8).cpu().float() - exp).abs().float().mean() < 0.5, tile
+        I.assert_codes_close(_nchw(o8).cpu(), exp, f"stem_mfma int8 tile {tile}")
     if (k, cout) == (7, 64):
         # relu + int8 (the config-4 stem): the per-wave kernel's med3 + v_cvt_pk_u8 epilogue
         # gives the same codes as the all-blocks kernel's float chain (same MFMA sums)
@@ -1319,8 +1323,10 @@ def test_conv_i8(Cin, Cout, k, stride, dil, res, mode, variant):
     B, H = 2, 17
     x8 = torch.randint(-127, 128, (B, Cin, H, H), generator=g, dtype=torch.int32)
     w8 = torch.randint(-127, 128, (Cout, Cin, k, k), generator=g, dtype=torch.int32)
-    sc = torch.rand(Cout, generator=g) * 1e-4
-    bi = torch.randn(Cout, generator=g)
+    # accumulators have a standard deviation of 5376 sqrt(Cin k^2) (5376: that of a product of
+    # two uniform +-127 codes): ~40 output steps of 0.05 after scaling, so the codes stay interior
+    sc = (0.5 + torch.rand(Cout, generator=g)) * 0.05 * 40 / (5376 * (Cin * k * k) ** 0.5)
+    bi = torch.randn(Cout, generator=g) * 10 * 0.05
     acc = F.conv2d(x8.double(), w8.double(), None, stride, dil * (k // 2), dil)  # exact
     ref = acc.float() * sc.view(1, -1, 1, 1) + bi.view(1, -1, 1, 1)
     OH, OW = ref.shape[-2:]
@@ -1339,6 +1345,8 @@ def test_conv_i8(Cin, Cout, k, stride, dil, res, mode, variant):
                   out_scale=0.05, variant=variant)
         torch.cuda.synchronize()
         exp = torch.clamp(torch.round(ref / 0.05), -127, 127)
+        sat = (exp.abs() == 127).float().mean().item()
+        assert sat <= 0.05 and (exp > 0).float().mean() > 0.3, sat  # an error is not hidden by the clamp
         diff = (_nchw(out).cpu().float() - exp).abs()
         assert diff.max() <= 1 and (diff > 0).float().mean() < 1e-3
     else:
@@ -1347,6 +1355,142 @@ def test_conv_i8(Cin, Cout, k, stride, dil, res, mode, variant):
                   Cout=Cout, k=k, stride=stride, dil=dil, act="relu", variant=variant)
         torch.cuda.synchronize()
         assert _rel(_nchw(out).cpu(), ref) < 5e-3
+
+
+# (Cout, ldo, co_off, output): every store path of the conv_i8 epilogues
+_I8_LAYOUTS = [(64, 192, 64, "i8"),    # aligned 16-byte stores into a channel slice
+               (64, 200, 72, "i8"),    # slice at an 8-byte offset: the byte-store fallback
+               (40, 40, 0, "i8"),      # channel tail (40 = 2 x 16 + 8)
+               (19, 24, 0, "bf16"),    # the logits row: 19 channels in a row of 24
+               (21, 24, 0, "bf16"),
+               (64, 68, 4, "bf16")]    # bf16 slice that no 16-byte store reaches
+
+
+def _i8_epilogue_case(k, dil, Cout, seed):
+    """Operands of the epilogue test, scaled so the codes stay interior: accumulators have a
+    standard deviation of 5376 sqrt(Cin k^2) (5376: that of a product of two uniform +-127
+    codes), so scale = u * out_scale * 40 / that puts ~40 output steps on them; bias and the
+    per-image bias ~ N(0, (10 steps)^2), the residual adds 0.3 steps per code."""
+    g = torch.Generator().manual_seed(seed)
+    B, H, Cin, out_scale = 2, 13, 128, 0.05
+    x8 = torch.randint(-127, 128, (B, Cin, H, H), generator=g, dtype=torch.int32)
+    w8 = torch.randint(-127, 128, (Cout, Cin, k, k), generator=g, dtype=torch.int32)
+    sc = (0.5 + torch.rand(Cout, generator=g)) * out_scale * 40 / (5376 * (Cin * k * k) ** 0.5)
+    bi = torch.randn(Cout, generator=g) * 10 * out_scale
+    ib = torch.randn(B, Cout, generator=g) * 10 * out_scale
+    r8 = torch.randint(-127, 128, (B, Cout, H, H), generator=g, dtype=torch.int32)
+    return dict(B=B, H=H, Cin=Cin, out_scale=out_scale, res_scale=0.3 * out_scale, x8=x8, w8=w8, sc=sc,
+                bi=bi, ib=ib, r8=r8)
+
+
+@pytest.mark.parametrize("Cout,ldo,co_off,mode", _I8_LAYOUTS)
+@pytest.mark.parametrize("k,dil", [(1, 1), (3, 5)])
+def test_conv_i8_epilogue(k, dil, Cout, ldo, co_off, mode):
+    """Every ``conv_i8`` variant against a float64 reference computed on the CPU (never
+    against another variant), over the epilogue's branches: act None / relu / relu6, with and
+    without a per-image bias, with and without an int8 residual, into every output layout.
+    B = 2, 13 x 13 (M = 338: partial tiles that straddle the image boundary), Cin = 128.
+    int8: at most one step off on <= 1e-3 of the codes; bf16: 2^-8 relative + 1e-6 elementwise.
+    The neighbours of a channel slice and the padding of a row keep their sentinel. With
+    act None the codes reach -127 and never -128, in the reference and in the output. The
+    saturated share of the reference is asserted <= 5 % (measured on the CPU: <= 1.5 %)."""
+    import int8_ref as I
+    from semantic_segmentation_server_amd.models.hip_int8 import _I8_VARIANTS
+    K = _hip()
+    c = _i8_epilogue_case(k, dil, Cout, seed=41 + k)
+    B, H, Cin, s_out = c["B"], c["H"], c["Cin"], c["out_scale"]
+    i8 = mode == "i8"
+    variants = list(_I8_VARIANTS) + [12, 13]
+    if K.conv_i8_1x1_ok(Cin=Cin, Cout=Cout, k=k, ldo=ldo, co_off=co_off, int8_out=i8):
+        variants += [5, 6, 10, 11]
+    xin = _nhwc(c["x8"].to(torch.int8)).to(DEV)
+    wk = c["w8"].to(torch.int8).permute(0, 2, 3, 1).contiguous().to(DEV)
+    sc, bi, ib = c["sc"].to(DEV), c["bi"].to(DEV), c["ib"].to(DEV)
+    rin = _nhwc(c["r8"].to(torch.int8)).to(DEV)
+    sentinel = 99 if i8 else float("nan")
+    worst = (0.0, 0)
+    for act in (None, "relu", "relu6"):
+        for img in (False, True):
+            for res in (False, True):
+                v = I.exact_conv(c["x8"], c["w8"], c["sc"], c["bi"], 1.0, dil=dil,
+                                 res_codes=c["r8"] if res else None, s_res=c["res_scale"],
+                                 img_bias=c["ib"] if img else None, act=act)
+                ref = I.requant(v, s_out) if i8 else v
+                if i8:
+                    assert I.saturated_share(ref) <= 0.05, (act, img, res, I.saturated_share(ref))
+                    assert int(ref.min()) == (-127 if act is None else 0)
+                    if act == "relu6":
+                        assert int(ref.max()) == 120  # 6 / 0.05: the relu6 cap is live
+                for variant in variants:
+                    what = f"variant {variant} act {act} img_bias {img} res {res}"
+                    out = torch.full((B, H, H, ldo), sentinel, dtype=torch.int8 if i8 else torch.bfloat16,
+                                     device=DEV)
+                    K.conv_i8(xin, wk, sc, bi, out, B=B, IH=H, IW=H, Cin=Cin, OH=H, OW=H, Cout=Cout, k=k,
+                              dil=dil, ldo=ldo, co_off=co_off, act=act, res=rin if res else None,
+                              res_scale=c["res_scale"], img_bias=ib if img else None,
+                              out_scale=s_out if i8 else None, variant=variant)
+                    torch.cuda.synchronize()
+                    o = out.cpu()
+                    got = _nchw(o[..., co_off:co_off + Cout])
+                    rest = torch.cat([o[..., :co_off], o[..., co_off + Cout:]], -1)
+                    if i8:
+                        assert bool((rest == 99).all()), what + ": wrote outside its channel slice"
+                        share, mx = I.assert_codes_close(got, ref, what)
+                        worst = max(worst, (share, mx))
+                        if act is None:
+                            assert int(got.min()) == -127, what
+                    else:
+                        assert bool(torch.isnan(rest.float()).all()), what + ": wrote outside its channel slice"
+                        I.assert_bf16_close(got, ref, what)
+    print(f"conv_i8 epilogue k={k} {(Cout, ldo, co_off, mode)}: {len(variants)} variants, worst mismatch "
+          f"share {worst[0]:.2e}, max step {worst[1]}")
+
+
+@pytest.mark.parametrize("variant", [7, 2, 4, 8])
+def test_conv_i8_epilogue_tap_group_perm(variant):
+    """The 3x3 dilation-5 case of ``test_conv_i8_epilogue`` with the rows permuted into
+    tap-uniform tiles (``tap_group_perm``), against the same float64 reference."""
+    import int8_ref as I
+    K = _hip()
+    k, dil, Cout, ldo, co_off = 3, 5, 64, 192, 64
+    c = _i8_epilogue_case(k, dil, Cout, seed=41 + k)
+    B, H, Cin, s_out = c["B"], c["H"], c["Cin"], c["out_scale"]
+    v = I.exact_conv(c["x8"], c["w8"], c["sc"], c["bi"], 1.0, dil=dil, res_codes=c["r8"],
+                     s_res=c["res_scale"], img_bias=c["ib"], act="relu")
+    ref = I.requant(v, s_out)
+    assert I.saturated_share(ref) <= 0.05
+    perm = K.tap_group_perm(B, H, H, 3, dil, K.I8_TILE[variant][0], device=DEV)
+    assert perm.numel() > B * H * H  # more than one tap class: padded tiles
+    out = torch.full((B, H, H, ldo), 99, dtype=torch.int8, device=DEV)
+    K.conv_i8(_nhwc(c["x8"].to(torch.int8)).to(DEV), c["w8"].to(torch.int8).permute(0, 2, 3, 1).contiguous().to(DEV),
+              c["sc"].to(DEV), c["bi"].to(DEV), out, B=B, IH=H, IW=H, Cin=Cin, OH=H, OW=H, Cout=Cout, k=k,
+              dil=dil, ldo=ldo, co_off=co_off, act="relu", res=_nhwc(c["r8"].to(torch.int8)).to(DEV),
+              res_scale=c["res_scale"], img_bias=c["ib"].to(DEV), out_scale=s_out, variant=variant, perm=perm)
+    torch.cuda.synchronize()
+    o = out.cpu()
+    assert bool((o[..., :co_off] == 99).all()) and bool((o[..., co_off + Cout:] == 99).all())
+    I.assert_codes_close(_nchw(o[..., co_off:co_off + Cout]), ref, f"variant {variant} with perm")
+
+
+@pytest.mark.parametrize("IH,IW,C", [(65, 65, 64), (12, 9, 16), (1, 7, 32)])
+def test_maxpool_i8(IH, IW, C):
+    """``maxpool3x3s2_i8`` on codes over the whole -128..127 range, bit-equal to
+    ``F.max_pool2d(x, 3, 2, 1)``: the padding never wins, not even over a window that holds
+    only -128 (the first and the last window of image 0 do)."""
+    K = _hip()
+    g = torch.Generator().manual_seed(51)
+    B = 2
+    x = torch.randint(-128, 128, (B, C, IH, IW), generator=g, dtype=torch.int32)
+    x[0, :, :2, :2] = -128  # all-negative windows at two borders
+    x[0, :, -2:, -2:] = -128
+    x[1, :, :2, :2] = torch.randint(-128, -100, (C, min(2, IH), 2), generator=g, dtype=torch.int32)
+    ref = F.max_pool2d(x.float(), 3, 2, 1)
+    OH, OW = ref.shape[-2:]
+    assert ref[0, :, 0, 0].max() == -128 and ref.min() == -128 and ref.max() == 127
+    out = torch.full((B, OH, OW, C), 99, dtype=torch.int8, device=DEV)
+    K.maxpool3x3s2_i8(_nhwc(x.to(torch.int8)).to(DEV), out, B=B, IH=IH, IW=IW, C=C, OH=OH, OW=OW)
+    torch.cuda.synchronize()
+    assert torch.equal(_nchw(out).cpu().float(), ref)
 
 
 def test_conv_i8_k64_rows_bit_identical():
@@ -1535,9 +1679,12 @@ def test_int8_resnet50_headline_shape():
     (assets/tune_mi355x.json) -- the 160x128 LDS-DMA tiles, streaming 1x1 / 3x3 kernels
     at the grids that produce the bench number.
 
-    Checked layer by layer with teacher forcing: every backbone conv's int8 output codes
-    against exact integer arithmetic on the plan's OWN input codes (quant.int8_conv_codes):
-    at most one step off, on <= 1e-3 of the codes. End to end the random-init int8 network
+    Checked step by step with teacher forcing (tests/int8_ref.py ``check_plan``, the walker
+    of tests/test_int8_plan.py on the picked variants): the int8 stem, the int8 max pool,
+    every backbone conv, the ASPP branches and the projection against exact arithmetic on the
+    plan's OWN input codes (at most one step off, on <= 1e-3 of the codes; the pool
+    bit-equal), the pooled branch's per-image bias, the bf16 logits and the label map of the
+    plan's own logits. End to end the random-init int8 network
     is chaotic -- a one-step rounding tie flipped in block 0 doubles its share of mismatched
     codes every block (scripts/int8_layer_diff.py: 2e-5 at block 0, 0.6 at block 15, with the
     stem modelled exactly) -- so the logits' distance to the fp32 fake-quant replay is bounded
@@ -1545,7 +1692,7 @@ def test_int8_resnet50_headline_shape():
     import json
     from semantic_segmentation_server_amd import config as C
     from semantic_segmentation_server_amd.models.hip_model import TUNE_FILE_DEFAULT
-    from semantic_segmentation_server_amd.models.quant import fake_quant_forward, int8_conv_codes
+    from semantic_segmentation_server_amd.models.quant import fake_quant_forward
     from semantic_segmentation_server_amd.ops import reference_ops as R
     from semantic_segmentation_server_amd.runtime.engine import Engine
     from semantic_segmentation_server_amd.runtime.sources import SyntheticSource
@@ -1567,33 +1714,13 @@ def test_int8_resnet50_headline_shape():
     assert torch.equal(got, again), "int8 plan reruns differ"
     assert all(saved[key].get(n) == v for n, v in hm.choices.items() if n in saved[key]), \
         "the plan under test is not the committed one"
-    Sc = hm.scales
-    nchw = lambda t: t.permute(0, 3, 1, 2).float()  # noqa: E731
-    worst = []
-    x = bufs["pool0"]
-    s_in = Sc["stem"]
-    for i, d in enumerate(hm.blocks):
-        m = d["blk"]
-        # (name, layer, input codes, s_in, s_out, residual codes, s_res, act: None = the layer's)
-        checks = [(f"r{i}_c1", m.conv1, x, s_in, Sc[f"b{i}.c1"], None, 0.0, None)]
-        checks.append((f"r{i}_c2", m.conv2, bufs[f"r{i}_c1"], Sc[f"b{i}.c1"], Sc[f"b{i}.c2"], None, 0.0, None))
-        if m.down is not None:
-            checks.append((f"r{i}_down", m.down, x, s_in, Sc[f"b{i}.down"], None, 0.0, None))
-            idt = bufs[f"r{i}_down"]
-        else:
-            idt = x
-        checks.append((f"r{i}_out", m.conv3, bufs[f"r{i}_c2"], Sc[f"b{i}.c2"], Sc[f"b{i}.out"], idt,
-                       d["s_res"], "relu"))
-        for name, layer, inp, si, so, res, sr, act in checks:
-            ref = int8_conv_codes(layer, nchw(inp), si, so, None if res is None else nchw(res), sr,
-                                  act=act)
-            dlt = (nchw(bufs[name]).to(torch.int32) - ref).abs()
-            worst.append((name, (dlt > 0).float().mean().item(), int(dlt.max())))
-        x, s_in = bufs[f"r{i}_out"], Sc[f"b{i}.out"]
-    for name, frac_, mx in worst:
-        assert mx <= 1 and frac_ <= 1e-3, (name, frac_, mx)
-    print("teacher-forced per-layer mismatch: worst " +
-          str(max(worst, key=lambda w: w[1])))
+    # every step of the committed plan as this run left it (the picks only), each against exact
+    # arithmetic on the step's own input buffers; the references stay on the device
+    import int8_ref as I
+    rep = I.check_plan(hm, hm._plans[(B, ch, cw)][0], bufs, frames, eng.lut_x, eng.lut_y, run=False,
+                       ref_device=DEV, interior=False)
+    assert len(rep) == 2 + 16 * 3 + 4 + 2, len(rep)  # stem, pool, 52 backbone convs, ASPP, projection
+    print("teacher-forced per-step mismatch: worst " + str(I.worst(rep)))
     x = R.preprocess(frames.cpu(), eng.lut_x.cpu(), eng.lut_y.cpu()).to(DEV)
     import copy
     m32 = copy.deepcopy(eng.model).float().to(DEV)
