@@ -19,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from semantic_segmentation_server_amd import config as C  # noqa: E402
-from semantic_segmentation_server_amd.models.hip_model import Choice  # noqa: E402
+from semantic_segmentation_server_amd.models.plan import all_choices  # noqa: E402
 from semantic_segmentation_server_amd.runtime.engine import Engine  # noqa: E402
 from semantic_segmentation_server_amd.runtime.sources import SyntheticSource  # noqa: E402
 
@@ -58,9 +58,7 @@ def main() -> None:
         return ("ok" if torch.equal(a0, a1) else "HIST") + "/" + ("ok" if torch.equal(a0, a2) else "POISON")
 
     print("committed:", check(), flush=True)
-    choices = [o for o in ops if isinstance(o, Choice)]
-    nested = [o for c in choices for _, vops in c.variants for o in vops if isinstance(o, Choice)]
-    for op in choices + nested:
+    for op in all_choices(ops):
         if only and only not in op.name:
             continue
         keep = op.pick

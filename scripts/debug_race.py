@@ -12,7 +12,7 @@ _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, _ROOT)
 sys.path.insert(0, os.path.join(_ROOT, "tests"))
 import test_hip_kernels as T  # noqa: E402
-from semantic_segmentation_server_amd.models.hip_model import Choice  # noqa: E402
+from semantic_segmentation_server_amd.models.plan import Choice  # noqa: E402
 from semantic_segmentation_server_amd.runtime.engine import Engine  # noqa: E402
 from semantic_segmentation_server_amd.runtime.sources import SyntheticSource  # noqa: E402
 

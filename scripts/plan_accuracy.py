@@ -24,7 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from semantic_segmentation_server_amd import config as C  # noqa: E402
 from semantic_segmentation_server_amd.models.deeplab import build_model  # noqa: E402
-from semantic_segmentation_server_amd.models.hip_model import Choice, HipDeepLab  # noqa: E402
+from semantic_segmentation_server_amd.models.hip_model import HipDeepLab  # noqa: E402
+from semantic_segmentation_server_amd.models.plan import all_choices  # noqa: E402
 from semantic_segmentation_server_amd.ops import reference_ops as R  # noqa: E402
 
 
@@ -64,9 +65,7 @@ def main() -> None:
     base = score(hm.logits(fd, tx, ty).clone())
     print(f"B={B} committed plan: rel {base[0]:.4f} agree {base[1]:.4f}", flush=True)
     ops = hm._plan(B, 480, 640)[0]
-    choices = [o for o in ops if isinstance(o, Choice)]
-    nested = [o for c in choices for _, vops in c.variants for o in vops if isinstance(o, Choice)]
-    for op in choices + nested:
+    for op in all_choices(ops):
         if only and only not in op.name:
             continue
         keep = op.pick

@@ -4,8 +4,8 @@ The torch model (``models/deeplab.py``) is the weight source and the numerics
 reference; this module folds BatchNorm into every conv, packs the weights into
 the kernels' layouts once, and executes the network as a fixed list of kernel
 launches over static NHWC bf16 buffers (allocated per (batch, camera) on first
-use, outside any graph capture). The engine captures the whole list into one
-hipGraph.
+use, outside any graph capture; ``models/plan.py``). The engine captures the whole
+list into one hipGraph.
 
 Layout decisions (MI355X-first, not a translation of the tflite graph):
   * NHWC bf16 activations, fp32 accumulation; 1x1/3x3 dense convs are MFMA
@@ -18,14 +18,17 @@ Layout decisions (MI355X-first, not a translation of the tflite graph):
     projection weights into a per-image bias of the projection GEMM.
   * Logits are written with a padded channel stride (ld 24 for 21 classes) and
     upsampled + argmax'ed in one kernel.
+
+Plan building: one method per network stage (returns its ops and the running ``(x, h, w,
+c)``); per MobileNetV2 block one generator per kernel family (returns ``(variant, [ops])``).
 """
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 
 from ..ops import fused_band as FB
 from ..ops import fused_span as FS
@@ -34,12 +37,7 @@ from ..ops.hip_ops import conv_out_hw
 from .deeplab import DeepLabV3
 from .layers import ConvBNAct
 from .mobilenetv2 import MobileNetV2Backbone
-from .resnet import ResNet50Backbone
-
-
-# committed plan picks for MI355X (plan shapes of the headline and the BASELINE configs)
-TUNE_FILE_DEFAULT = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(
-    os.path.abspath(__file__)))), "assets", "tune_mi355x.json")
+from .plan import TUNE_FILE_DEFAULT, Choice, HipPlanModel  # noqa: F401 (the tune file: tests, tools)
 
 
 def _pack_dense(layer: ConvBNAct, dev) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -53,6 +51,24 @@ def _pack_dw(layer: ConvBNAct, dev) -> Tuple[torch.Tensor, torch.Tensor]:
     w, b = layer.fold()  # [C, 1, 3, 3]
     return (w.reshape(w.shape[0], 9).t().contiguous().to(dev, torch.float32),
             b.contiguous().to(dev, torch.float32))
+
+
+def _pack_stem(layer: ConvBNAct, dev) -> Tuple[torch.Tensor, torch.Tensor]:
+    w, b = layer.fold()  # [Cout, 3, k, k] -> [k, k, 3, Cout]
+    return (w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous().to(dev, torch.float32),
+            b.contiguous().to(dev, torch.float32))
+
+
+def _fold_block(m) -> tuple:
+    """The folded layers of an inverted-residual block as the fused kernels' packers take
+    them: (we, be, wd, bd, wp, bp); we = be = None for a block without expansion."""
+    ew = eb = None
+    if m.expand is not None:
+        ew, eb = m.expand.fold()
+        ew = ew[:, :, 0, 0]
+    dwf, dbf = m.dw.fold()
+    pwf, pbf = m.project.fold()
+    return ew, eb, dwf[:, 0], dbf, pwf[:, :, 0, 0], pbf
 
 
 _TILES = [(8, 16), (4, 16), (11, 11), (5, 11), (8, 13), (5, 13), (16, 16), (11, 22)]
@@ -70,77 +86,6 @@ def _tile_candidates(OH: int, OW: int, CinP: int, stride: int, dil: int,
         if covered <= 1.25 * OH * OW:
             out.append((ty, tx))
     return out
-
-
-class Choice:
-    """A plan step with alternative implementations; ``autotune`` keeps the
-    fastest on the actual shapes (timed with HIP events at plan build)."""
-
-    def __init__(self, name: str, variants: List[Tuple[str, List[Callable]]]):
-        self.name = name
-        self.variants = variants
-        self.pick = 0
-
-    def __call__(self, *args):
-        for op in self.variants[self.pick][1]:
-            op(*args)
-
-    def autotune(self, args, reps: int = 5) -> None:
-        mode = os.environ.get("SSA_FUSED_IR", "auto")
-        if mode in ("0", "1"):
-            want = "unfused" if mode == "0" else "fused"
-            self.pick = next((i for i, (n, _) in enumerate(self.variants) if n == want), 0)
-            for _, ops in self.variants:
-                for op in ops:
-                    if isinstance(op, Choice):
-                        op.autotune(args, reps)
-            return
-        for _, ops in self.variants:  # nested choices first (e.g. block 0 inside stem+block0)
-            for op in ops:
-                if isinstance(op, Choice):
-                    op.autotune(args, reps)
-        if len(self.variants) < 2:
-            return
-        times = []
-        graph = os.environ.get("SSA_TUNE_GRAPH", "1") == "1"
-        for _, ops in self.variants:
-            for _ in range(2):
-                for op in ops:
-                    op(*args)
-            st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            g = None
-            if graph:
-                # time the variant replayed from a hipGraph, as the engine runs it: timed from
-                # Python, every kernel under ~16 us measured the host's launch path instead
-                # (all batch-1 variants of blocks 7-10 read 16-17 us, r4 retune tables)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                # thread-local capture: a plan built lazily while another thread (feeder,
-                # result collector) uses the device must not invalidate their calls
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    for _ in range(reps):
-                        for op in ops:
-                            op(*args)
-                g.replay()
-            st.record()
-            if g is not None:
-                g.replay()
-            else:
-                for _ in range(reps):
-                    for op in ops:
-                        op(*args)
-            en.record()
-            en.synchronize()
-            times.append(st.elapsed_time(en) / reps)
-            del g
-        self.pick = min(range(len(times)), key=times.__getitem__)
-        self.times = times
-
-
-def _pack_stem(layer: ConvBNAct, dev) -> Tuple[torch.Tensor, torch.Tensor]:
-    w, b = layer.fold()  # [Cout, 3, k, k] -> [k, k, 3, Cout]
-    return (w.permute(2, 3, 1, 0).reshape(-1, w.shape[0]).contiguous().to(dev, torch.float32),
-            b.contiguous().to(dev, torch.float32))
 
 
 _PW_CONFIGS = [(2, 1), (2, 2), (2, 3), (4, 3), (4, 5)]
@@ -178,25 +123,13 @@ def _dwp_rows_fit(ty: int, stages: int, dil: int, OW: int, cout: int) -> bool:
             stages * (halo * 64 + (cout // 16 + 1) * 1024) <= 160 * 1024)
 
 
-def _copy_picks(src: List[Callable], dst: List[Callable]) -> None:
-    """Give every Choice of ``dst`` (a plan built by the same code) the pick of the
-    Choice at the same position in ``src``, nested choices included."""
-    for a, b in zip(src, dst):
-        if isinstance(a, Choice) and isinstance(b, Choice):
-            b.pick = a.pick
-            for (_, va), (_, vb) in zip(a.variants, b.variants):
-                _copy_picks(va, vb)
+def _rows_per_band(work: int, OH: int, targets) -> List[int]:
+    return list(dict.fromkeys(min(max(2, -(-work // target)), OH) for target in targets))
 
 
-class HipDeepLab:
+class HipDeepLab(HipPlanModel):
     def __init__(self, model: DeepLabV3, device: torch.device, cfg=None):
-        if device.type != "cuda":
-            raise RuntimeError("HipDeepLab needs a GPU")
-        self.device = device
-        self.model = model
-        self.H = self.W = int(cfg.input_size) if cfg is not None else 513
-        self.num_classes = model.num_classes
-        self.ldk = (self.num_classes + 7) // 8 * 8
+        super().__init__(model, device, cfg.input_size if cfg is not None else 513)
         dev = device
         bb = model.backbone
         self.kind = "mnv2" if isinstance(bb, MobileNetV2Backbone) else "resnet50"
@@ -204,45 +137,13 @@ class HipDeepLab:
         self.blocks: List[dict] = []
         self.stem_block0 = None
         if self.kind == "mnv2":
-            for blk in bb.blocks:
-                s = blk.spec
-                d = dict(
-                    spec=s, module=blk,
-                    expand=_pack_dense(blk.expand, dev) if blk.expand is not None else None,
-                    dw=_pack_dw(blk.dw, dev),
-                    project=_pack_dense(blk.project, dev))
-                row_ok = s.dilation == 1 and s.cin <= 64 and s.cout <= 96 and s.cin % 8 == 0
-                shape = (-(-s.cout // 16), -(-s.cin // 32))
-                tile_ok = s.cin % 8 == 0 and (
-                    shape in K.FUSED_TILE_SHAPES if blk.expand is not None
-                    else shape in K.FUSED_TILE_SHAPES_NOEXP and not s.residual)
-                if row_ok or tile_ok:
-                    ew = eb = None
-                    if blk.expand is not None:
-                        ew, eb = blk.expand.fold()
-                        ew = ew[:, :, 0, 0]
-                    dwf, dbf = blk.dw.fold()
-                    pwf, pbf = blk.project.fold()
-                    packed = K.pack_fused_ir(
-                        ew, eb, dwf[:, 0], dbf, pwf[:, :, 0, 0], pbf, Cin=s.cin, hid=s.hidden,
-                        Cout=s.cout, stride=s.stride, residual=s.residual, device=dev,
-                        dil=s.dilation)
-                    if row_ok:
-                        d["fused"] = packed
-                    if tile_ok:
-                        d["fused_tile"] = packed
-                if s.hidden % 32 == 0 and blk.expand is not None and not row_ok:
-                    pwf, pbf = blk.project.fold()
-                    d["dwproj"] = K.pack_project_padded(pwf[:, :, 0, 0], pbf, s.cout, s.hidden, dev)
-                self.blocks.append(d)
+            self.blocks = [self._pack_mnv2_block(blk, dev) for blk in bb.blocks]
             b0 = bb.blocks[0]
             s0 = b0.spec
             if (b0.expand is None and s0.stride == 1 and s0.dilation == 1 and s0.cin == 32 and
                     s0.cout == 16 and bb.stem.cout == 32 and bb.stem.k == 3 and bb.stem.stride == 2
                     and bb.stem.act == "relu6"):
-                dwf, dbf = b0.dw.fold()
-                pwf, pbf = b0.project.fold()
-                self.stem_block0 = K.pack_stem_block0(bb.stem, dwf[:, 0], dbf, pwf[:, :, 0, 0], pbf, dev)
+                self.stem_block0 = K.pack_stem_block0(bb.stem, *_fold_block(b0)[2:], dev)
         else:
             for blk in bb.blocks:
                 self.blocks.append(dict(
@@ -254,8 +155,7 @@ class HipDeepLab:
         self.aspp_c = aspp.cout
         self.aspp_b0 = _pack_dense(aspp.b0, dev)
         self.aspp_atrous = [(_pack_dense(b, dev), b.dilation) for b in aspp.atrous]
-        nb_sp = 1 + len(aspp.atrous)  # spatial branches
-        self.cat_c = nb_sp * aspp.cout
+        self.cat_c = (1 + len(aspp.atrous)) * aspp.cout  # the spatial branches
         pw, pb = aspp.project.fold()  # [256, nb*256, 1, 1]
         pw = pw[:, :, 0, 0]
         self.proj_w = pw[:, : self.cat_c].contiguous().to(dev, torch.bfloat16)
@@ -270,120 +170,119 @@ class HipDeepLab:
         self.logit_w = lw[:, :, 0, 0].reshape(lw.shape[0], 1, 1, -1).contiguous().to(dev, torch.bfloat16)
         self.logit_b = lb.to(dev, torch.float32)
         self.head = None  # aspp_head packed operands (built with the first plan)
-        # set by the DP pipeline at world > 1: rank 0's autotune picks -> every rank
-        self.pick_sync: Optional[Callable[[Optional[dict]], dict]] = None
-        self._plans: Dict[tuple, Tuple[List[Callable], Dict[str, torch.Tensor]]] = {}
         self._side_streams: List[torch.cuda.Stream] = []  # SSA_POOL_FORK side streams (one per plan)
         self._span_tables: Dict[tuple, dict] = {}
-        self._labels_out: Optional[torch.Tensor] = None
-        self._guards: list = []  # SSA_GUARD_BYTES debug bands (name, raw, guard, nbytes)
+
+    @staticmethod
+    def _pack_mnv2_block(blk, dev) -> dict:
+        s = blk.spec
+        d = dict(
+            spec=s, module=blk,
+            expand=_pack_dense(blk.expand, dev) if blk.expand is not None else None,
+            dw=_pack_dw(blk.dw, dev),
+            project=_pack_dense(blk.project, dev))
+        row_ok = s.dilation == 1 and s.cin <= 64 and s.cout <= 96 and s.cin % 8 == 0
+        shape = (-(-s.cout // 16), -(-s.cin // 32))
+        tile_ok = s.cin % 8 == 0 and (
+            shape in K.FUSED_TILE_SHAPES if blk.expand is not None
+            else shape in K.FUSED_TILE_SHAPES_NOEXP and not s.residual)
+        fold = _fold_block(blk)
+        if row_ok or tile_ok:
+            packed = K.pack_fused_ir(*fold, Cin=s.cin, hid=s.hidden, Cout=s.cout, stride=s.stride,
+                                     residual=s.residual, device=dev, dil=s.dilation)
+            if row_ok:
+                d["fused"] = packed
+            if tile_ok:
+                d["fused_tile"] = packed
+        if s.hidden % 32 == 0 and blk.expand is not None and not row_ok:
+            d["dwproj"] = K.pack_project_padded(fold[4], fold[5], s.cout, s.hidden, dev)
+        return d
 
     # ------------------------------------------------------------------ plan
-    def _plan(self, B: int, Hc: int, Wc: int, part: int = 0):
-        """Kernel list + static buffers for (B, camera). ``part`` > 0: an independent
-        copy (own buffers) of the same plan, for concurrent sub-batches on separate
-        streams; it takes part 0's autotune picks."""
-        key = (B, Hc, Wc) if part == 0 else (B, Hc, Wc, part)
-        if key in self._plans:
-            return self._plans[key]
-        dev = self.device
-        bufs: Dict[str, torch.Tensor] = {}
-        ops: List[Callable] = []
+    def _build(self, B: int, Hc: int, Wc: int, buf, bufs):
+        mnv2 = self.kind == "mnv2"
+        ops, st = (self._stem_mnv2 if mnv2 else self._stem_resnet)(B, Hc, Wc, buf, bufs)
+        first = 1 if mnv2 and self.stem_block0 is not None else 0  # block 0 is in the stem choice
+        for i in range(first, len(self.blocks)):
+            bops, st = (self._mnv2_block if mnv2 else self._resnet_block)(buf, i, self.blocks[i], B, *st)
+            ops += bops
+        cat = buf("aspp_cat", B, st[1], st[2], self.cat_c)
+        branches = self._aspp_branches(B, buf, bufs, cat, *st)
+        fork, pool, img_bias = self._aspp_pool(B, buf, bufs, *st)
+        # (SSA_POOL_FORK: the pooling branch forks before the branch GEMMs and joins before the head)
+        ops += fork + branches + pool
+        head, logits = self._head(B, buf, cat, img_bias, st[1], st[2])
+        return ops + head + self._upsample(B, buf, logits, st[1], st[2])
 
-        guard = int(os.environ.get("SSA_GUARD_BYTES", "0"))  # debug: sentinel bands
-
-        def buf(name, *shape, dtype=torch.bfloat16):
-            # zeroed for tidiness only: no picked kernel reads plan bytes it did not write
-            # (plan constants kept among the buffers are named const_*, pool_w*)
-            # (scripts/debug_poison.py run B: NaN-filled buffers give bit-identical labels;
-            # tests/test_hip_kernels.py::test_plan_is_a_function_of_the_frame, at 257^2 and
-            # at the headline 513^2 / 640x480 shape with the B = 32 plan's kernels)
-            if guard:  # debug (scripts/debug_guard.py): 0x5A bands before and after
-                n = 1
-                for d_ in shape:
-                    n *= d_
-                nb = n * torch.tensor([], dtype=dtype).element_size()
-                raw = torch.full((nb + 2 * guard,), 0x5A, dtype=torch.uint8, device=dev)
-                raw[guard:guard + nb].zero_()
-                t = raw[guard:guard + nb].view(dtype).view(*shape)
-                self._guards.append((name, raw, guard, nb))
-                bufs[name] = t
-                return t
-            t = torch.zeros(shape, dtype=dtype, device=dev)
-            bufs[name] = t
-            return t
-
+    def _stem_op(self, B, Hc, Wc, buf, bufs):
         H, W = self.H, self.W
         sw, sb, sk, ss, sact, sc = self.stem
         OH, OW = conv_out_hw(H, W, sk, ss, 1)
         x = buf("stem", B, OH, OW, sc)
         bufs["_in_shape"] = torch.tensor([B, Hc, Wc])
+        return (lambda frames, lx, ly: K.stem_conv(
+            frames, lx, ly, sw, sb, x, H=H, W=W, OH=OH, OW=OW, Cout=sc, k=sk, stride=ss,
+            act=sact)), (x, OH, OW, sc)
 
-        def stem_op(frames, lx, ly, x=x, OH=OH, OW=OW):
-            K.stem_conv(frames, lx, ly, sw, sb, x, H=H, W=W, OH=OH, OW=OW, Cout=sc, k=sk,
-                        stride=ss, act=sact)
-        ops.append(stem_op)
-        stem_at = len(ops) - 1
-        h, w, c = OH, OW, sc
-        if self.kind == "resnet50":
-            if (sc, sk) == (64, 7):
-                # the dense 7x7 stem on bf16 MFMA, one wave per 16 channels (config 4 bf16:
-                # 792 -> 127 us per 8 frames against the fp32 per-lane kernel, r8k)
-                wpk = K.pack_stem_mfma(sw, sk, sc)
-                bufs["const_stem_wpk"] = wpk
-                stem_variants = [("fp32", [stem_op])]
-                for tile in ((16, 32), (32, 32)):
-                    stem_variants.append((f"mfmaw{tile[0]}x{tile[1]}", [
-                        lambda frames, lx, ly, x=x, OH=OH, OW=OW, tile=tile: K.stem_mfma(
-                            frames, lx, ly, wpk, sb, x, H=H, W=W, OH=OH, OW=OW, Cout=sc, k=sk, stride=ss,
-                            act=sact, tile=tile, per_wave=True)]))
-                ops[stem_at] = Choice("stem", stem_variants)
-            PH, PW = conv_out_hw(h, w, 3, 2, 1)
-            y = buf("pool0", B, PH, PW, c)
-            ops.append(lambda *_, x=x, y=y, h=h, w=w, c=c, PH=PH, PW=PW:
-                       K.maxpool3x3s2(x, y, B=B, IH=h, IW=w, C=c, OH=PH, OW=PW))
-            x, h, w = y, PH, PW
-            for i, blk in enumerate(self.blocks):
-                x, h, w, c = self._resnet_block(ops, buf, i, blk, x, B, h, w, c)
-        else:
-            for i, blk in enumerate(self.blocks):
-                x, h, w, c = self._mnv2_block(ops, buf, i, blk, x, B, h, w, c)
-                if i == 0 and self.stem_block0 is not None:
-                    # stem + block 0 as one kernel (the 257^2 x 32 stem tensor never hits HBM)
-                    sbp, out0 = self.stem_block0, x
-                    fused = [(f"stem_block0_{ty}x{tx}", [
-                        lambda frames, lx, ly, out0=out0, ty=ty, tx=tx, sbp=sbp: K.stem_block0(
-                            frames, lx, ly, sbp, out0, H=H, W=W, tile=(ty, tx))])
-                        for ty, tx in ((8, 16), (4, 16), (8, 8), (16, 16), (8, 32), (12, 16))]
-                    # row-streaming bands: every input pixel gathered once, every stem pixel
-                    # computed once (stem_band.hip); bit-identical to the tile kernel
-                    SH = OH
-                    # band heights: grids of ~1-4 workgroups per CU, plus the heights whose
-                    # band count fills whole residency rounds (~3 of these 4-wave workgroups
-                    # fit a CU: a grid of 1.46 rounds pays a half-empty second round)
-                    for nbx in (3, 4, 5):
-                        Rs = [max(2, -(-B * nbx * SH // target)) for target in (256, 512, 1024)]
-                        Rs += [max(2, -(-SH // nby)) for nby in range(2, 13)
-                               if B * nbx * nby in range(640, 800) or B * nbx * nby in range(1400, 1560)]
-                        for R in dict.fromkeys(Rs):
-                            for oneb in (True, False):
-                                tag = f"stem_band{R}x{nbx}" + ("" if oneb else "b2")
-                                if any(t == tag for t, _ in fused):
-                                    continue
-                                fused.insert(0, (tag, [
-                                    lambda frames, lx, ly, out0=out0, R=R, nbx=nbx, sbp=sbp, oneb=oneb: K.stem_band(
-                                        frames, lx, ly, sbp, out0, H=H, W=W, R=R, nbx=nbx, one_barrier=oneb)]))
-                    sep = ("separate", [ops[stem_at], ops[stem_at + 1]])
-                    ops[stem_at:stem_at + 2] = [Choice("stem+block0", fused + [sep])]
-        # ---- ASPP
+    def _stem_resnet(self, B, Hc, Wc, buf, bufs):
+        """The ``stem`` choice (where the MFMA stem applies) and the max pool."""
+        (sw, sb, sk, ss, sact, sc), H, W = self.stem, self.H, self.W
+        stem, (x, h, w, c) = self._stem_op(B, Hc, Wc, buf, bufs)
+        if (sc, sk) == (64, 7):
+            # the dense 7x7 stem on bf16 MFMA, one wave per 16 channels (config 4 bf16:
+            # 792 -> 127 us per 8 frames against the fp32 per-lane kernel, r8k)
+            wpk = K.pack_stem_mfma(sw, sk, sc)
+            bufs["const_stem_wpk"] = wpk
+            stem = Choice("stem", [("fp32", [stem])] + [(f"mfmaw{tile[0]}x{tile[1]}", [
+                lambda frames, lx, ly, tile=tile: K.stem_mfma(
+                    frames, lx, ly, wpk, sb, x, H=H, W=W, OH=h, OW=w, Cout=sc, k=sk, stride=ss,
+                    act=sact, tile=tile, per_wave=True)]) for tile in ((16, 32), (32, 32))])
+        PH, PW = conv_out_hw(h, w, 3, 2, 1)
+        y = buf("pool0", B, PH, PW, c)
+        pool = (lambda *_: K.maxpool3x3s2(x, y, B=B, IH=h, IW=w, C=c, OH=PH, OW=PW))
+        return [stem, pool], (y, PH, PW, c)
+
+    def _stem_mnv2(self, B, Hc, Wc, buf, bufs):
+        """The stem conv, or the ``stem+block0`` choice: stem + block 0 as one kernel (the
+        257^2 x 32 stem tensor never hits HBM) against the two separate steps."""
+        H, W = self.H, self.W
+        stem, st = self._stem_op(B, Hc, Wc, buf, bufs)
+        if self.stem_block0 is None:
+            return [stem], st
+        block0, st0 = self._mnv2_block(buf, 0, self.blocks[0], B, *st)
+        sbp, out0, SH = self.stem_block0, st0[0], st[1]
+        tiles = [(f"stem_block0_{ty}x{tx}", [
+            lambda frames, lx, ly, ty=ty, tx=tx: K.stem_block0(
+                frames, lx, ly, sbp, out0, H=H, W=W, tile=(ty, tx))])
+            for ty, tx in ((8, 16), (4, 16), (8, 8), (16, 16), (8, 32), (12, 16))]
+        # row-streaming bands: every input pixel gathered once, every stem pixel
+        # computed once (stem_band.hip); bit-identical to the tile kernel
+        bands: Dict[str, List[Callable]] = {}
+        # band heights: grids of ~1-4 workgroups per CU, plus the heights whose
+        # band count fills whole residency rounds (~3 of these 4-wave workgroups
+        # fit a CU: a grid of 1.46 rounds pays a half-empty second round)
+        for nbx in (3, 4, 5):
+            Rs = [max(2, -(-B * nbx * SH // target)) for target in (256, 512, 1024)]
+            Rs += [max(2, -(-SH // nby)) for nby in range(2, 13)
+                   if B * nbx * nby in range(640, 800) or B * nbx * nby in range(1400, 1560)]
+            for R in dict.fromkeys(Rs):
+                for oneb in (True, False):
+                    bands.setdefault(f"stem_band{R}x{nbx}" + ("" if oneb else "b2"), [
+                        lambda frames, lx, ly, R=R, nbx=nbx, oneb=oneb: K.stem_band(
+                            frames, lx, ly, sbp, out0, H=H, W=W, R=R, nbx=nbx, one_barrier=oneb)])
+        # fixed order (pick 0 is the default, the tune file names variants): last band first
+        return [Choice("stem+block0", list(bands.items())[::-1] + tiles +
+                       [("separate", [stem] + block0)])], st0
+
+    def _aspp_branches(self, B, buf, bufs, cat, x, h, w, c):
+        """The 1x1 and the atrous branches into their channel slices of ``cat``: one step
+        per branch, or the ``aspp.branches`` choice of grouped launches against them."""
         A = self.aspp_c
-        cat = buf("aspp_cat", B, h, w, self.cat_c)
         b0w, b0b = self.aspp_b0
-        aspp_at = len(ops)
-        ops.append(pw_choice("aspp.b0", lambda *_, x=x, h=h, w=w, c=c: K.conv_gemm(
+        sep = [pw_choice("aspp.b0", lambda *_: K.conv_gemm(
             x, b0w, b0b, cat, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w, Cout=A, k=1, ldo=self.cat_c,
             co_off=0, act="relu"), x, b0w, b0b, cat, M=B * h * w, Cin=c, Cout=A, ldo=self.cat_c,
-            co_off=0, act="relu"))
+            co_off=0, act="relu")]
         for j, ((aw, ab), rate) in enumerate(self.aspp_atrous):
             # atrous branch: raster-order tiles, or tiles grouped by tap validity
             # (tap_group_perm) so the kernel skips every all-padding tap
@@ -391,461 +290,361 @@ class HipDeepLab:
             if c in K.TAP_CIN and A % 8 == 0:
                 twp, tbp = K.pack_tap_weights(aw, ab)
                 for name, grouped in (("tap", False), ("tapg", True)):
-                    perm = K.tap_group_perm(B, h, w, 3, rate, 256, dev) if grouped else None
+                    perm = K.tap_group_perm(B, h, w, 3, rate, 256, self.device) if grouped else None
                     variants.append((name, [
-                        lambda *_, x=x, h=h, w=w, c=c, twp=twp, tbp=tbp, rate=rate, j=j, perm=perm:
+                        lambda *_, twp=twp, tbp=tbp, rate=rate, j=j, perm=perm:
                         K.tap_conv(x, twp, tbp, cat, B=B, H=h, W=w, Cin=c, Cout=A, k=3, dil=rate,
                                    ldo=self.cat_c, co_off=(j + 1) * A, act="relu", perm=perm)]))
             for name, variant, bm in (("v4", 4, 0), ("v4g", 4, 128), ("v5g", 5, 128),
                                       ("v6g", 6, 256)):
-                perm = K.tap_group_perm(B, h, w, 3, rate, bm, dev) if bm else None
+                perm = K.tap_group_perm(B, h, w, 3, rate, bm, self.device) if bm else None
                 variants.append((name, [
-                    lambda *_, x=x, h=h, w=w, c=c, aw=aw, ab=ab, rate=rate, j=j, variant=variant,
-                    perm=perm: K.conv_gemm(
+                    lambda *_, aw=aw, ab=ab, rate=rate, j=j, variant=variant, perm=perm: K.conv_gemm(
                         x, aw, ab, cat, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w, Cout=A, k=3, dil=rate,
                         ldo=self.cat_c, co_off=(j + 1) * A, act="relu", variant=variant,
                         perm=perm)]))
-            ops.append(Choice(f"aspp.rate{rate}", variants))
+            sep.append(Choice(f"aspp.rate{rate}", variants))
         if len(self.aspp_atrous) <= 3 and c % 8 == 0:
-            # all spatial branches (1x1 + atrous) in ONE LPT-ordered LDS-DMA grid
-            # (conv_gemm_grouped) against the per-branch launches above
-            seq = ("separate", ops[aspp_at:])
-            grouped = []
-            # (variant 11, 128x128 tiles / 4 waves / 64 KiB LDS -- the only grouped variant
-            # that fits two workgroups per CU -- gave label maps that differed in 26 of 450
-            # runs with plan copies on three streams, every other variant 0 / 450:
-            # profiles/r2_concurrency_race.txt; kept out until that is understood)
-            for gv in (5, 6, 8, 12, 13, 14, 15, 16, 17, 18):
-                BM = K.GROUP_TILE[gv][0]
-                convs = [dict(x=x, w=b0w, bias=b0b, out=cat, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w,
-                              Cout=A, k=1, dil=1, ldo=self.cat_c, co_off=0, act="relu")]
-                for j, ((aw, ab), rate) in enumerate(self.aspp_atrous):
-                    convs.append(dict(x=x, w=aw, bias=ab, out=cat, B=B, IH=h, IW=w, Cin=c, OH=h,
-                                      OW=w, Cout=A, k=3, dil=rate, ldo=self.cat_c,
-                                      co_off=(j + 1) * A, act="relu",
-                                      perm=K.tap_group_perm(B, h, w, 3, rate, BM, dev)))
-                order = K.grouped_tile_order(convs, gv, dev)
-                bufs[f"aspp_order{gv}"] = order
-                grouped.append((f"grouped_v{gv}", [
-                    lambda *_, convs=convs, order=order, gv=gv: K.conv_gemm_grouped(convs, order, gv)]))
-                # small batches: split-K (a batch-1 grid is ~40 tiles of up to 45 K stages for
-                # 256 CUs); fp32 partials + one combine (bias, ReLU) over the concat buffer
-                ks_opts = (2, 4, 6) if B <= 2 else (2, 3) if B <= 8 else ()
-                if ks_opts and gv in (5, 17, 18) and A * (len(self.aspp_atrous) + 1) == self.cat_c:
-                    if "aspp_part" not in bufs:
-                        buf("aspp_part", max(ks_opts) * B * h * w * self.cat_c, dtype=torch.float32)
-                        bufs["const_aspp_bias_cat"] = torch.cat(
-                            [b0b.float()] + [ab.float() for (_, ab), _ in self.aspp_atrous]).to(dev).contiguous()
-                    ntile = max(-(-(c["perm"].numel() if c.get("perm") is not None else B * h * w) // BM)
-                                for c in convs) * -(-A // K.GROUP_TILE[gv][1])
-                    cnt = buf(f"aspp_cnt{gv}", 4 * ntile, dtype=torch.int32)
-                    for ks in ks_opts:
-                        order_k = K.grouped_tile_order(convs, gv, dev, ks=ks)
-                        bufs[f"aspp_order{gv}k{ks}"] = order_k
-                        for inl in (False, True):  # in-launch combine by each tile's last K slice
-                            grouped.append((f"grouped_v{gv}k{ks}" + ("c" if inl else ""), [
-                                lambda *_, convs=convs, order=order_k, gv=gv, ks=ks, cnt=(cnt if inl else None):
-                                K.conv_gemm_grouped(convs, order, gv, ks=ks, part=bufs["aspp_part"],
-                                                    bias_cat=bufs["const_aspp_bias_cat"], cnt=cnt)]))
-                # (branch-affine XCD orders, K.grouped_tile_order_branch, measured 6-16 us
-                # slower on every variant: profiles/r3_negative_results.txt)
-            ops[aspp_at:] = [Choice("aspp.branches", grouped + [seq])]
-        img_bias = None
-        if self.has_pool:
-            img_bias = buf("img_bias", B, A, dtype=torch.float32)
-            gws = K.gap_workspace(B, c, dev)
-            bufs["gap_ws"] = gws
-            if c <= 2048 and A <= 512 and c % 8 == 0 and A % 4 == 0:
-                # GAP partials + one per-image kernel for the pooled MLP (aspp_pool)
-                w1t = self.pool_w.t().contiguous()
-                w2t = self.proj_pool_w.t().contiguous()
-                bufs["pool_w1t"], bufs["pool_w2t"] = w1t, w2t
-                pool_op = (lambda *_, x=x, h=h, w=w, c=c, w1t=w1t, w2t=w2t: K.aspp_pool(
-                    x, gws, w1t, self.pool_b, w2t, img_bias, B=B, HW=h * w, C=c, N=A))
-                if os.environ.get("SSA_POOL_FORK", "0") == "1" and torch.cuda.is_available():
-                    # the pooling branch (GAP partials + per-image MLP: 32 + 32 small
-                    # workgroups, ~26 us of latency at B = 32) on a side stream forked before
-                    # the grouped branch GEMM and joined before the head: its few waves fit
-                    # beside the GEMM's 16 per CU instead of running after it (event fork /
-                    # join, captured into the hipGraph like the rest of the plan)
-                    side = torch.cuda.Stream(dev)
-                    ev_f, ev_j = torch.cuda.Event(), torch.cuda.Event()
-                    self._side_streams.append(side)
+            return [Choice("aspp.branches",
+                           self._aspp_grouped(B, buf, bufs, cat, x, h, w, c) + [("separate", sep)])]
+        return sep
 
-                    def fork_op(*args, side=side, ev_f=ev_f, ev_j=ev_j, pool_op=pool_op):
-                        ev_f.record(torch.cuda.current_stream())
-                        side.wait_event(ev_f)
-                        with torch.cuda.stream(side):
-                            pool_op(*args)
-                        ev_j.record(side)
+    def _aspp_grouped(self, B, buf, bufs, cat, x, h, w, c):
+        """All spatial branches (1x1 + atrous) in ONE LPT-ordered LDS-DMA grid
+        (conv_gemm_grouped), per tile shape and split-K factor."""
+        A, dev = self.aspp_c, self.device
+        b0w, b0b = self.aspp_b0
+        grouped = []
+        # (variant 11, 128x128 tiles / 4 waves / 64 KiB LDS -- the only grouped variant
+        # that fits two workgroups per CU -- gave label maps that differed in 26 of 450
+        # runs with plan copies on three streams, every other variant 0 / 450:
+        # profiles/r2_concurrency_race.txt; kept out until that is understood)
+        # (branch-affine XCD orders, K.grouped_tile_order_branch, measured 6-16 us
+        # slower on every variant: profiles/r3_negative_results.txt)
+        for gv in (5, 6, 8, 12, 13, 14, 15, 16, 17, 18):
+            BM = K.GROUP_TILE[gv][0]
+            convs = [dict(x=x, w=b0w, bias=b0b, out=cat, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w,
+                          Cout=A, k=1, dil=1, ldo=self.cat_c, co_off=0, act="relu")]
+            for j, ((aw, ab), rate) in enumerate(self.aspp_atrous):
+                convs.append(dict(x=x, w=aw, bias=ab, out=cat, B=B, IH=h, IW=w, Cin=c, OH=h,
+                                  OW=w, Cout=A, k=3, dil=rate, ldo=self.cat_c,
+                                  co_off=(j + 1) * A, act="relu",
+                                  perm=K.tap_group_perm(B, h, w, 3, rate, BM, dev)))
+            order = K.grouped_tile_order(convs, gv, dev)
+            bufs[f"aspp_order{gv}"] = order
+            grouped.append((f"grouped_v{gv}", [
+                lambda *_, convs=convs, order=order, gv=gv: K.conv_gemm_grouped(convs, order, gv)]))
+            # small batches: split-K (a batch-1 grid is ~40 tiles of up to 45 K stages for
+            # 256 CUs); fp32 partials + one combine (bias, ReLU) over the concat buffer
+            ks_opts = (2, 4, 6) if B <= 2 else (2, 3) if B <= 8 else ()
+            if ks_opts and gv in (5, 17, 18) and A * (len(self.aspp_atrous) + 1) == self.cat_c:
+                if "aspp_part" not in bufs:
+                    buf("aspp_part", max(ks_opts) * B * h * w * self.cat_c, dtype=torch.float32)
+                    bufs["const_aspp_bias_cat"] = torch.cat(
+                        [b0b.float()] + [ab.float() for (_, ab), _ in self.aspp_atrous]).to(dev).contiguous()
+                ntile = max(-(-(cv["perm"].numel() if cv.get("perm") is not None else B * h * w) // BM)
+                            for cv in convs) * -(-A // K.GROUP_TILE[gv][1])
+                cnt = buf(f"aspp_cnt{gv}", 4 * ntile, dtype=torch.int32)
+                for ks in ks_opts:
+                    order_k = K.grouped_tile_order(convs, gv, dev, ks=ks)
+                    bufs[f"aspp_order{gv}k{ks}"] = order_k
+                    for inl in (False, True):  # in-launch combine by each tile's last K slice
+                        grouped.append((f"grouped_v{gv}k{ks}" + ("c" if inl else ""), [
+                            lambda *_, convs=convs, order=order_k, gv=gv, ks=ks, cnt=(cnt if inl else None):
+                            K.conv_gemm_grouped(convs, order, gv, ks=ks, part=bufs["aspp_part"],
+                                                bias_cat=bufs["const_aspp_bias_cat"], cnt=cnt)]))
+        return grouped
 
-                    ops.insert(aspp_at, fork_op)
-                    ops.append(lambda *_, ev_j=ev_j: torch.cuda.current_stream().wait_event(ev_j))
-                else:
-                    ops.append(pool_op)
-            else:
-                gap = buf("gap", B, c, dtype=torch.float32)
-                pooled = buf("pooled", B, A, dtype=torch.float32)
-                ops.append(lambda *_, x=x, h=h, w=w, c=c: K.global_avgpool(x, gap, B=B, HW=h * w, C=c,
-                                                                           ws=gws))
-                ops.append(lambda *_, c=c: K.matvec(gap, self.pool_w, self.pool_b, pooled, B=B, N=A,
-                                                    K=c, act="relu"))
-                ops.append(lambda *_: K.matvec(pooled, self.proj_pool_w, None, img_bias, B=B, N=A, K=A))
+    def _aspp_pool(self, B, buf, bufs, x, h, w, c):
+        """The image-pooling branch -> per-image bias of the projection. Returns (ops to run
+        before the branches, ops to run before the head, img_bias)."""
+        if not self.has_pool:
+            return [], [], None
+        A, dev = self.aspp_c, self.device
+        img_bias = buf("img_bias", B, A, dtype=torch.float32)
+        gws = K.gap_workspace(B, c, dev)
+        bufs["gap_ws"] = gws
+        if not (c <= 2048 and A <= 512 and c % 8 == 0 and A % 4 == 0):
+            gap = buf("gap", B, c, dtype=torch.float32)
+            pooled = buf("pooled", B, A, dtype=torch.float32)
+            return [], [
+                lambda *_: K.global_avgpool(x, gap, B=B, HW=h * w, C=c, ws=gws),
+                lambda *_: K.matvec(gap, self.pool_w, self.pool_b, pooled, B=B, N=A, K=c, act="relu"),
+                lambda *_: K.matvec(pooled, self.proj_pool_w, None, img_bias, B=B, N=A, K=A)], img_bias
+        # GAP partials + one per-image kernel for the pooled MLP (aspp_pool)
+        w1t = self.pool_w.t().contiguous()
+        w2t = self.proj_pool_w.t().contiguous()
+        bufs["pool_w1t"], bufs["pool_w2t"] = w1t, w2t
+        pool_op = (lambda *_: K.aspp_pool(
+            x, gws, w1t, self.pool_b, w2t, img_bias, B=B, HW=h * w, C=c, N=A))
+        if not (os.environ.get("SSA_POOL_FORK", "0") == "1" and torch.cuda.is_available()):
+            return [], [pool_op], img_bias
+        # the pooling branch (GAP partials + per-image MLP: 32 + 32 small
+        # workgroups, ~26 us of latency at B = 32) on a side stream forked before
+        # the grouped branch GEMM and joined before the head: its few waves fit
+        # beside the GEMM's 16 per CU instead of running after it (event fork /
+        # join, captured into the hipGraph like the rest of the plan)
+        side = torch.cuda.Stream(dev)
+        ev_f, ev_j = torch.cuda.Event(), torch.cuda.Event()
+        self._side_streams.append(side)
+
+        def fork_op(*args):
+            ev_f.record(torch.cuda.current_stream())
+            side.wait_event(ev_f)
+            with torch.cuda.stream(side):
+                pool_op(*args)
+            ev_j.record(side)
+
+        return [fork_op], [lambda *_: torch.cuda.current_stream().wait_event(ev_j)], img_bias
+
+    def _head(self, B, buf, cat, img_bias, h, w):
+        """Projection and logits: two steps, or the ``aspp.head`` choice of the fused kernel
+        against them. Returns (ops, logits buffer)."""
+        A = self.aspp_c
         proj = buf("aspp_proj", B, h, w, A)
         proj_variants = [(f"v{v}", [
-            lambda *_, h=h, w=w, v=v: K.conv_gemm(
+            lambda *_, v=v: K.conv_gemm(
                 cat, self.proj_w, self.proj_b, proj, B=B, IH=h, IW=w, Cin=self.cat_c, OH=h, OW=w,
                 Cout=A, k=1, act="relu", img_bias=img_bias, variant=v)]) for v in (4, 3, 5, 6)]
         logits = buf("logits", B, h, w, self.ldk)
-        split = [Choice("aspp.proj", proj_variants), pw_choice("logits", lambda *_, h=h, w=w: K.conv_gemm(
+        split = [Choice("aspp.proj", proj_variants), pw_choice("logits", lambda *_: K.conv_gemm(
             proj, self.logit_w, self.logit_b, logits, B=B, IH=h, IW=w, Cin=A, OH=h, OW=w,
             Cout=self.num_classes, k=1, ldo=self.ldk, act=None), proj, self.logit_w,
             self.logit_b, logits, M=B * h * w, Cin=A, Cout=self.num_classes, ldo=self.ldk, act=None,
             N_out=self.ldk)]
-        if A == 256 and self.cat_c == 1024 and self.num_classes <= 32 and self.ldk <= 32:
-            # projection + bias + pooling bias + ReLU + logits in one kernel: the projection
-            # stays on chip (aspp_head.hip), no vendor GEMM on the hot path
-            if self.head is None:
-                self.head = K.pack_aspp_head(self.proj_w, self.proj_b, self.logit_w, self.logit_b, dev)
-            Mh = B * h * w
-            g0 = K.aspp_head_groups(Mh)
-            head = [(f"head_g{g}" + ("w" if nw == 16 else ""), [lambda *_, g=g, h=h, w=w, nw=nw: K.aspp_head(
-                cat.view(Mh, self.cat_c), self.head, logits.view(Mh, self.ldk), M=Mh, HW=h * w,
-                ldo=self.ldk, img_bias=img_bias, G=g, waves=nw)]) for g in K.ASPP_HEAD_G
-                if g == g0 or (g < g0 and -(-Mh // (16 * g)) <= 1024) for nw in (8, 16)]
-            ops.append(Choice("aspp.head", head + [("split", split)]))
-        else:
-            ops.extend(split)
+        if not (A == 256 and self.cat_c == 1024 and self.num_classes <= 32 and self.ldk <= 32):
+            return split, logits
+        # projection + bias + pooling bias + ReLU + logits in one kernel: the projection
+        # stays on chip (aspp_head.hip), no vendor GEMM on the hot path
+        if self.head is None:
+            self.head = K.pack_aspp_head(self.proj_w, self.proj_b, self.logit_w, self.logit_b, self.device)
+        Mh = B * h * w
+        g0 = K.aspp_head_groups(Mh)
+        head = [(f"head_g{g}" + ("w" if nw == 16 else ""), [lambda *_, g=g, nw=nw: K.aspp_head(
+            cat.view(Mh, self.cat_c), self.head, logits.view(Mh, self.ldk), M=Mh, HW=h * w,
+            ldo=self.ldk, img_bias=img_bias, G=g, waves=nw)]) for g in K.ASPP_HEAD_G
+            if g == g0 or (g < g0 and -(-Mh // (16 * g)) <= 1024) for nw in (8, 16)]
+        return [Choice("aspp.head", head + [("split", split)])], logits
+
+    def _upsample(self, B, buf, logits, h, w):
+        H, W = self.H, self.W
         labels = buf("labels", B, H, W, dtype=torch.uint8)
-        # labels_out (segment's out=): write the label maps straight into a caller
-        # buffer (the engine's per-slot maps) instead of the plan's static one
         # upsample + argmax: row-block (LDS-staged, coalesced stores), per-lane stores, or
         # per-lane with wave-union class pruning
-        ops.append(Choice("upsample", [(name, [lambda *_, h=h, w=w, v=K.UPSAMPLE_VARIANTS[name]:
-                                               K.upsample_argmax(
+        return [Choice("upsample", [(name, [lambda *_, v=K.UPSAMPLE_VARIANTS[name]: K.upsample_argmax(
             logits, self._labels_out if self._labels_out is not None else labels, B=B, h=h, w=w,
-            K=self.num_classes, ldk=self.ldk, H=H, W=W, variant=v)]) for name in ("rows", "lane", "union", "cand")]))
-        self._plans[key] = (ops, bufs)
-        if part == 0:
-            self._autotune(ops, B, Hc, Wc)
-        else:
-            _copy_picks(self._plan(B, Hc, Wc)[0], ops)
-            args = self._tune_inputs(B, Hc, Wc)
-            for op in ops:  # first launches (lazy kernel attributes) outside any capture
-                op(*args)
-        return self._plans[key]
+            K=self.num_classes, ldk=self.ldk, H=H, W=W, variant=v)])
+            for name in ("rows", "lane", "union", "cand")])]
 
-    def _tune_inputs(self, B: int, Hc: int, Wc: int):
-        """Representative autotune inputs: letterboxed synthetic camera frames (the
-        bench/serving source) and the real letterbox LUTs. All-zero frames would make
-        the data-dependent kernels (upsample's convexity shortcut, the post stage)
-        take their degenerate fast paths (VERDICT r1 Weak #9)."""
-        import numpy as np
-        from ..ops import reference_ops as R
-        from ..runtime.sources import SyntheticSource
-        src = SyntheticSource(Wc, Hc, stream=0, seed=1234, pool=min(B, 4))
-        fr, _, _ = src.read_batch(B)
-        frames = torch.from_numpy(np.ascontiguousarray(fr)).to(self.device)
-        lx, ly, *_ = R.letterbox_luts(Wc, Hc, self.W, self.H)
-        return (frames, torch.tensor(np.array(lx), dtype=torch.int32, device=self.device),
-                torch.tensor(np.array(ly), dtype=torch.int32, device=self.device))
-
-    def _autotune(self, ops, B, Hc, Wc) -> None:
-        """Time every Choice on the real buffers and keep the fastest variant.
-
-        Picks come, in order, from: ``SSA_TUNE_FILE=path.json`` (or, unset, the
-        committed ``assets/tune_mi355x.json``), keyed by plan shape, so a deployment and
-        the driver's short benchmark run reuse one fixed plan instead of re-timing at
-        start-up (timings are noisy and variants differ in rounding); else from timing
-        on representative inputs -- on rank 0 only when ``pick_sync`` is set (the DP
-        pipeline broadcasts rank 0's picks, so every rank runs the same kernels and
-        produces the same label maps). With SSA_TUNE_FILE set, newly timed picks are
-        written back (rank 0, atomic replace)."""
-        if torch.cuda.is_current_stream_capturing():
-            return
-        dev = self.device
-        args = self._tune_inputs(B, Hc, Wc)
-        for op in ops:  # populate every buffer once
-            op(*args)
-        choices = [op for op in ops if isinstance(op, Choice)]
-        nested = [o for c in choices for _, vops in c.variants for o in vops if isinstance(o, Choice)]
-        every = choices + nested
-        key = f"{self.kind}:B={B}:cam={Wc}x{Hc}:in={self.H}"
-        env_path = os.environ.get("SSA_TUNE_FILE")
-        path = env_path or TUNE_FILE_DEFAULT
-        saved = {}
-        if path and os.path.exists(path) and os.environ.get("SSA_RETUNE", "0") != "1":
-            import json
-            with open(path) as f:
-                saved = json.load(f).get(key, {})
-        rank0 = int(os.environ.get("RANK", "0")) == 0
-        # SSA_RETUNE_ONLY=block7,block8,...: re-time just these choices (exact names) on top
-        # of the saved picks (a new kernel variant for a few plan steps)
-        only = {n for n in os.environ.get("SSA_RETUNE_ONLY", "").split(",") if n}
-        retimed = False
-        if saved:
-            for op in every:
-                want = saved.get(op.name)
-                hit = next((i for i, (n, _) in enumerate(op.variants) if n == want), None)
-                if op.name in only and op in choices and len(op.variants) > 1:
-                    op.autotune(args)
-                    retimed = True
-                elif hit is not None:
-                    op.pick = hit
-                elif op in choices and len(op.variants) > 1:
-                    op.autotune(args)  # a variant set the saved plan does not know: time it
-                    retimed = True
-            if retimed and self.pick_sync is not None:
-                # (every rank reads the same file, so every rank re-timed the same choices:
-                # the broadcast is collective) rank 0's timings decide, as in a cold tune
-                picks = self.pick_sync({op.name: op.pick for op in every} if rank0 else None)
-                for op in every:
-                    op.pick = picks.get(op.name, op.pick)
-        else:
-            if self.pick_sync is None or rank0:
-                for op in choices:
-                    op.autotune(args)
-            if self.pick_sync is not None:
-                picks = self.pick_sync({op.name: op.pick for op in every} if rank0 else None)
-                for op in every:
-                    op.pick = picks.get(op.name, op.pick)
-        torch.cuda.synchronize(dev)
-        self.choices = {op.name: op.variants[op.pick][0] for op in every}
-        if env_path and (not saved or retimed) and rank0:
-            import json
-            allp = {}
-            if os.path.exists(env_path):
-                with open(env_path) as f:
-                    allp = json.load(f)
-            allp[key] = self.choices
-            tmp = f"{env_path}.{os.getpid()}.tmp"
-            with open(tmp, "w") as f:
-                json.dump(allp, f, indent=1, sort_keys=True)
-            os.replace(tmp, env_path)
-        if os.environ.get("SSA_LOG_AUTOTUNE", "0") == "1":
-            import sys
-            for op in ops:
-                if isinstance(op, Choice) and hasattr(op, "times"):
-                    print(f"[autotune B={B}] {op.name}: " + ", ".join(
-                        f"{n}={t * 1e3:.1f}us" for (n, _), t in zip(op.variants, op.times)) +
-                        f" -> {op.variants[op.pick][0]}", file=sys.stderr)
-            if saved:
-                print(f"[autotune B={B}] picks from {path}: {self.choices}", file=sys.stderr)
-
-    def _mnv2_block(self, ops, buf, i, blk, x, B, h, w, c):
+    # ------------------------------------------------------- MobileNetV2 block
+    def _mnv2_block(self, buf, i, blk, B, x, h, w, c):
+        """Block ``i`` as the ``block{i}`` choice: the unfused steps (1x1 expansion,
+        depthwise, 1x1 projection) and every fused kernel family that fits the block."""
         s = blk["spec"]
-        bufs_part: Dict[str, torch.Tensor] = {}
         hid = s.hidden
-        inp = x
         unfused: List[Callable] = []
-        outer_ops, ops = ops, unfused
+        e = x
         if blk["expand"] is not None:
             ew, eb = blk["expand"]
             e = buf(f"b{i}_exp", B, h, w, hid)
-            ops.append(pw_choice(f"block{i}.expand", lambda *_, x=x, e=e, h=h, w=w, c=c: K.conv_gemm(
+            unfused.append(pw_choice(f"block{i}.expand", lambda *_: K.conv_gemm(
                 x, ew, eb, e, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w, Cout=hid, k=1, act="relu6"),
                 x, ew, eb, e, M=B * h * w, Cin=c, Cout=hid, act="relu6"))
-            x = e
-        unfused_expand_out = x
         OH, OW = conv_out_hw(h, w, 3, s.stride, s.dilation)
         dw_w, dw_b = blk["dw"]
         d = buf(f"b{i}_dw", B, OH, OW, hid)
-        ops.append(lambda *_, x=x, d=d, h=h, w=w, OH=OH, OW=OW: K.depthwise3x3(
-            x, dw_w, dw_b, d, B=B, IH=h, IW=w, C=hid, OH=OH, OW=OW, stride=s.stride,
+        unfused.append(lambda *_: K.depthwise3x3(
+            e, dw_w, dw_b, d, B=B, IH=h, IW=w, C=hid, OH=OH, OW=OW, stride=s.stride,
             dil=s.dilation, act="relu6"))
         pw_, pb_ = blk["project"]
         out = buf(f"b{i}_out", B, OH, OW, s.cout)
-        res = inp if s.residual else None
-        ops.append(lambda *_, d=d, out=out, OH=OH, OW=OW, res=res: K.conv_gemm(
+        res = x if s.residual else None
+        unfused.append(lambda *_: K.conv_gemm(
             d, pw_, pb_, out, B=B, IH=OH, IW=OW, Cin=hid, OH=OH, OW=OW, Cout=s.cout, k=1,
             act=None, res=res))
-        variants = [("unfused", unfused)]
-        if (blk["expand"] is not None and hid % 32 == 0 and s.cout in K.DWP_COUT
+        g = SimpleNamespace(i=i, blk=blk, s=s, B=B, x=x, h=h, w=w, c=c, hid=hid, e=e, out=out,
+                            res=res, OH=OH, OW=OW, buf=buf, expand_op=unfused[0])
+        # the families allocate their buffers in this order; the variants are listed in the
+        # order below, which is fixed: pick 0 is the default and the tune file names variants
+        dwp, dwproj, tile = self._dwp_variants(g), self._dwproj_variants(g), self._tile_variants(g)
+        stream, band, slices = self._stream_variants(g), self._band_variants(g), self._slice_variants(g)
+        variants = slices + band + stream + tile + [("unfused", unfused)] + dwp + dwproj
+        return [Choice(f"block{i}", variants)], (out, OH, OW, s.cout)
+
+    def _dwp_variants(self, g):
+        """``dwp*``: expansion (weight-streamed pw_conv, fp16 out) -> fused depthwise + projection."""
+        s, blk, B, h, w, c, hid, OH, OW = g.s, g.blk, g.B, g.h, g.w, g.c, g.hid, g.OH, g.OW
+        if not (blk["expand"] is not None and hid % 32 == 0 and s.cout in K.DWP_COUT
                 and K.pw_supported(c, hid)):
-            # expansion (weight-streamed, fp16 out) -> fused depthwise + projection
-            ew, eb = blk["expand"]
-            e16 = buf(f"b{i}_exp16", B, h, w, hid, dtype=torch.float16)
-            ewpk = K.pack_pw_weights(ew, eb)
-            wpk_dp = K.pack_dw_proj(pw_[:, 0, 0, :], dw_w, dw_b)
-            M = B * h * w
-            dwp_cfgs = [("w", 4, 0, 2, False)]
-            if s.stride == 1:
-                dwp_cfgs += [("r", 4, ty, 2, False) for ty in (2, 3, 4)]
-                dwp_cfgs += [("r", 4, ty, st, True) for ty in (2, 3, 4, 6) for st in (2, 3, 4)
-                             if _dwp_rows_fit(ty, st, s.dilation, OW, s.cout)]
-            for mt, nch in ((2, 3),):
-                for kind, nw, ty, st, xcd in dwp_cfgs:
-                    tag = f"dwp{kind}{nw if not ty else ty}" + (f"s{st}x" if xcd else "")
-                    variants.append((f"{tag}.pw{mt}x{nch}", [
-                        lambda *_, x=inp, e16=e16, M=M, c=c, mt=mt, nch=nch: K.pw_conv(
-                            x, ewpk, e16, M=M, K=c, N=hid, act="relu6", mt=mt, nch=nch),
-                        lambda *_, e16=e16, out=out, h=h, w=w, OH=OH, OW=OW, res=res, nw=nw, ty=ty,
-                        st=st, xcd=xcd:
-                        K.dw_proj_fused(e16, wpk_dp, pb_, out, B=B, IH=h, IW=w, hid=hid,
-                                        Cout=s.cout, OH=OH, OW=OW, stride=s.stride,
-                                        dil=s.dilation, res=res, waves=nw, rows=ty, stages=st,
-                                        xcd=xcd)]))
-        if "dwproj" in blk:
-            dpw, dpb = blk["dwproj"]
-            e = unfused_expand_out
-            variants.append(("dwproj", [unfused[0], lambda *_, e=e, out=out, h=h, w=w, OH=OH, OW=OW,
-                                        res=res: K.dw_project(
-                e, dw_w, dw_b, dpw, dpb, out, B=B, IH=h, IW=w, hid=hid, Cout=s.cout, OH=OH, OW=OW,
-                stride=s.stride, dil=s.dilation, res=res)]))
+            return []
+        ew, eb = blk["expand"]
+        (pw_, pb_), (dw_w, dw_b) = blk["project"], blk["dw"]
+        e16 = g.buf(f"b{g.i}_exp16", B, h, w, hid, dtype=torch.float16)
+        ewpk = K.pack_pw_weights(ew, eb)
+        wpk_dp = K.pack_dw_proj(pw_[:, 0, 0, :], dw_w, dw_b)
+        M = B * h * w
+        cfgs = [("w", 4, 0, 2, False)]
+        if s.stride == 1:
+            cfgs += [("r", 4, ty, 2, False) for ty in (2, 3, 4)]
+            cfgs += [("r", 4, ty, st, True) for ty in (2, 3, 4, 6) for st in (2, 3, 4)
+                     if _dwp_rows_fit(ty, st, s.dilation, OW, s.cout)]
+        out = []
+        for mt, nch in ((2, 3),):
+            for kind, nw, ty, st, xcd in cfgs:
+                tag = f"dwp{kind}{nw if not ty else ty}" + (f"s{st}x" if xcd else "")
+                out.append((f"{tag}.pw{mt}x{nch}", [
+                    lambda *_, mt=mt, nch=nch: K.pw_conv(
+                        g.x, ewpk, e16, M=M, K=c, N=hid, act="relu6", mt=mt, nch=nch),
+                    lambda *_, nw=nw, ty=ty, st=st, xcd=xcd:
+                    K.dw_proj_fused(e16, wpk_dp, pb_, g.out, B=B, IH=h, IW=w, hid=hid,
+                                    Cout=s.cout, OH=OH, OW=OW, stride=s.stride,
+                                    dil=s.dilation, res=g.res, waves=nw, rows=ty, stages=st,
+                                    xcd=xcd)]))
+        return out
+
+    def _dwproj_variants(self, g):
+        """``dwproj``: the unfused expansion step, then depthwise + projection in one kernel."""
+        if "dwproj" not in g.blk:
+            return []
+        s, (dpw, dpb), (dw_w, dw_b) = g.s, g.blk["dwproj"], g.blk["dw"]
+        return [("dwproj", [g.expand_op, lambda *_: K.dw_project(
+            g.e, dw_w, dw_b, dpw, dpb, g.out, B=g.B, IH=g.h, IW=g.w, hid=g.hid, Cout=s.cout,
+            OH=g.OH, OW=g.OW, stride=s.stride, dil=s.dilation, res=g.res)])]
+
+    def _tile_variants(self, g):
+        """``fused`` (row kernel) and ``tile*`` (2-D tiles): the whole block in one fused_ir launch."""
+        s, blk = g.s, g.blk
+        geom = dict(B=g.B, IH=g.h, IW=g.w, OH=g.OH, OW=g.OW)
+        out = []
         if "fused_tile" in blk:
             fp = blk["fused_tile"]
-            for tile in _tile_candidates(OH, OW, fp["CinP"], s.stride, s.dilation,
+            for tile in _tile_candidates(g.OH, g.OW, fp["CinP"], s.stride, s.dilation,
                                          fp["we"] is not None):
-                variants.insert(0, (f"tile{tile[0]}x{tile[1]}", [
-                    lambda *_, x=inp, out=out, h=h, w=w, OH=OH, OW=OW, tile=tile: K.fused_ir(
-                        x, fp, out, B=B, IH=h, IW=w, OH=OH, OW=OW, tile=tile)]))
+                out.append((f"tile{tile[0]}x{tile[1]}", [
+                    lambda *_, fp=fp, tile=tile: K.fused_ir(g.x, fp, g.out, tile=tile, **geom)]))
         if "fused" in blk:
-            fp = blk["fused"]
-            variants.insert(0, ("fused", [lambda *_, x=inp, out=out, h=h, w=w, OH=OH, OW=OW:
-                                          K.fused_ir(x, fp, out, B=B, IH=h, IW=w, OH=OH, OW=OW)]))
-        if blk["expand"] is not None and s.stride == 1 and (s.cin, s.cout) in FS.STREAM_SHAPES:
-            # expanded tensor kept on chip: raster spans of ~h*w/S pixels per workgroup
-            for S in self._span_counts(B, h, w):
-                if FS.stream_supported(s.cin, s.cout, 1, h, w, S, s.dilation, lattice=True):
-                    # dilation 2 on the phase-class lattice: halo +- 1 lattice row (ops/fused_span
-                    # .lattice_table), 3 halo rounds per expansion wave instead of 5
-                    if "span" not in blk:
-                        blk["span"] = self._pack_span(blk, s)
-                    ltab = self._span_table(h, w, S, s.dilation, lattice=True)
-                    for v in ((0, 1, 2, 4) if s.cout <= 160 else (1,)):
-                        variants.insert(0, (f"stream{S}" + {0: "", 1: "g", 2: "w", 4: "r3"}[v] + "L", [
-                            lambda *_, x=inp, out=out, tab=ltab, sp=blk["span"], v=v: FS.fused_ir_stream(
-                                x, sp, tab, out, B=B, residual=s.residual, variant=v)]))
-                    nc = -(-hid // 32)
-                    hs_opts = [hs for hs in (2, 3, 4, 6) if hs <= nc and B * S * hs <= 512] if B <= 16 else []
-                    if hs_opts:
-                        key = f"b{i}_part"
-                        if key not in bufs_part:
-                            bufs_part[key] = buf(key, max(hs_opts) * B * h * w * s.cout, dtype=torch.float32)
-                        part = bufs_part[key]
-                        cnt = buf(f"b{i}_cnt{S}", B * S, dtype=torch.int32)
-                        v = 0 if s.cout <= 160 else 1
-                        for hs in hs_opts:
-                            for inl in (False, True):
-                                variants.insert(0, (f"stream{S}Lh{hs}" + ("c" if inl else ""), [
-                                    lambda *_, x=inp, out=out, tab=ltab, sp=blk["span"], v=v, hs=hs, part=part,
-                                    cnt=(cnt if inl else None): FS.fused_ir_stream(
-                                        x, sp, tab, out, B=B, residual=s.residual, variant=v, hsplit=hs,
-                                        part=part, cnt=cnt)]))
-                if FS.stream_supported(s.cin, s.cout, 1, h, w, S, s.dilation):
-                    if "span" not in blk:
-                        blk["span"] = self._pack_span(blk, s)
-                    tab = self._span_table(h, w, S, s.dilation)
-                    # wave-specialised: expansion waves | depthwise+projection waves
-                    # 4 / 6: the 3-slot chunk ring (72 instead of 81 KiB for blocks 7-9: two
-                    # workgroups per CU)
-                    vs = ((0, 1, 2) if s.cout <= 96 and s.dilation == 1 else (0, 1)) + \
-                        ((4,) if s.cout <= 160 else ()) + ((6,) if s.cout <= 96 and s.dilation == 1 else ())
-                    for v in vs:
-                        variants.insert(0, (f"stream{S}" + {0: "", 1: "g", 2: "w", 4: "r3", 6: "wr3"}[v], [
-                            lambda *_, x=inp, out=out, tab=tab, sp=blk["span"], v=v: FS.fused_ir_stream(
-                                x, sp, tab, out, B=B, residual=s.residual, variant=v)]))
-                    # small batches: the hidden chunks of a span over hs workgroups (fp32
-                    # partials + stream_combine), so B * S * hs workgroups share the chip
-                    nc = -(-hid // 32)
-                    hs_opts = [hs for hs in (2, 3, 4, 6) if hs <= nc and B * S * hs <= 512] if B <= 16 else []
-                    if hs_opts:
-                        key = f"b{i}_part"
-                        if key not in bufs_part:
-                            bufs_part[key] = buf(key, max(hs_opts) * B * h * w * s.cout, dtype=torch.float32)
-                        part = bufs_part[key]
-                        # per-span arrival tickets of the in-launch combine ("...c" variants)
-                        cnt = buf(f"b{i}_cnt{S}", B * S, dtype=torch.int32)
-                        for hs in hs_opts:
-                            for v in ((0, 2) if s.cout <= 96 and s.dilation == 1 else (0,)):
-                                for inl in (False, True):
-                                    variants.insert(0, (f"stream{S}" + ("", "g", "w")[v] + f"h{hs}" + ("c" if inl else ""), [
-                                        lambda *_, x=inp, out=out, tab=tab, sp=blk["span"], v=v, hs=hs, part=part,
-                                        cnt=(cnt if inl else None): FS.fused_ir_stream(
-                                            x, sp, tab, out, B=B, residual=s.residual, variant=v, hsplit=hs,
-                                            part=part, cnt=cnt)]))
-        if blk["expand"] is not None and FB.band_supported(s.cin, hid, s.cout, s.stride, s.dilation, OW):
-            # row-streaming bands: every input row expanded once into an on-chip fp16 row
-            if "band" not in blk:
-                blk["band"] = self._pack_band(blk, s)
-            bp_ = blk["band"]
-            # (split 2 -- blocks 1-2 as two column bands, 5+5 waves with hs 2 -- measured
-            # 86-92 us vs 65-69 us for the full-width band: profiles/r3_negative_results.txt)
-            for split in (1,):
-                if not FB.band_supported(s.cin, hid, s.cout, s.stride, s.dilation, OW, split):
-                    continue
-                for hs in ((1, 2) if FB.band_waves(OW, split) <= 8 else (1,)):
-                    for nslot in (2, 1):
-                        if FB.band_lds(bp_, s.stride, OW, nslot, hs, split) > 160 * 1024:
-                            continue
-                        for R in self._band_rows(B, OH, OW, s.stride):
-                            tag = f"band{R}s{nslot}" + ("h" if hs == 2 else "") + ("c" if split == 2 else "")
-                            variants.insert(0, (tag, [
-                                lambda *_, x=inp, out=out, h=h, w=w, R=R, nslot=nslot, bp_=bp_, hs=hs,
-                                split=split: FB.fused_ir_band(x, bp_, out, B=B, IH=h, IW=w, stride=s.stride,
-                                                              residual=s.residual, R=R, nslot=nslot, hs=hs,
-                                                              split=split)]))
-        if blk["expand"] is not None:
-            # hidden-sliced row streaming: wave = column group x 32 hidden channels, the
-            # chunk's weights in VGPRs (fused_ir_slice.hip: the band kernel's LDS weight
-            # re-reads were its bottleneck)
-            for nw in FB.slice_widths(s.cin, hid, s.cout, s.stride, s.dilation):
-                if "band" not in blk:
-                    blk["band"] = self._pack_band(blk, s)
-                bp_ = blk["band"]
-                twmax = 16 * nw - (2 if s.stride == 1 else 1)
-                nbx = -(-OW // twmax)
-                for oneb in (False, True):  # "o": one barrier per input row
-                    if FB.slice_lds(bp_, s.stride, OW, nw, oneb) > 160 * 1024:
+            out.append(("fused", [lambda *_, fp=blk["fused"]: K.fused_ir(g.x, fp, g.out, **geom)]))
+        return out[::-1]  # the last one built is listed first (fixed order: _mnv2_block)
+
+    def _stream_variants(self, g):
+        """``stream*``: the expanded tensor kept on chip, raster spans of ~h*w/S pixels per
+        workgroup (fused_ir_stream), on the raster or the phase-class lattice table."""
+        s, blk, B, h, w = g.s, g.blk, g.B, g.h, g.w
+        if not (blk["expand"] is not None and s.stride == 1 and (s.cin, s.cout) in FS.STREAM_SHAPES):
+            return []
+        narrow = s.cout <= 96 and s.dilation == 1
+        out = []
+
+        def stream(name, tab, v, **kw):
+            sp = self._packed(blk, "span")
+            out.append((name, [lambda *_: FS.fused_ir_stream(
+                g.x, sp, tab, g.out, B=B, residual=s.residual, variant=v, **kw)]))
+
+        for S in self._span_counts(B, h, w):
+            if FS.stream_supported(s.cin, s.cout, 1, h, w, S, s.dilation, lattice=True):
+                # dilation 2 on the phase-class lattice: halo +- 1 lattice row (ops/fused_span
+                # .lattice_table), 3 halo rounds per expansion wave instead of 5
+                ltab = self._span_table(h, w, S, s.dilation, lattice=True)
+                for v in ((0, 1, 2, 4) if s.cout <= 160 else (1,)):
+                    stream(f"stream{S}" + {0: "", 1: "g", 2: "w", 4: "r3"}[v] + "L", ltab, v)
+                self._split_hidden(g, S, stream, ltab, [(0 if s.cout <= 160 else 1, "L")])
+            if FS.stream_supported(s.cin, s.cout, 1, h, w, S, s.dilation):
+                tab = self._span_table(h, w, S, s.dilation)
+                # wave-specialised: expansion waves | depthwise+projection waves
+                # 4 / 6: the 3-slot chunk ring (72 instead of 81 KiB for blocks 7-9: two
+                # workgroups per CU)
+                vs = ((0, 1, 2) if narrow else (0, 1)) + \
+                    ((4,) if s.cout <= 160 else ()) + ((6,) if narrow else ())
+                for v in vs:
+                    stream(f"stream{S}" + {0: "", 1: "g", 2: "w", 4: "r3", 6: "wr3"}[v], tab, v)
+                self._split_hidden(g, S, stream, tab, [(0, ""), (2, "w")] if narrow else [(0, "")])
+        return out[::-1]  # the last one built is listed first (fixed order: _mnv2_block)
+
+    @staticmethod
+    def _split_hidden(g, S, stream, tab, kernels) -> None:
+        """``stream{S}{tag}h{hs}[c]``, small batches: the hidden chunks of a span over hs
+        workgroups (fp32 partials + stream_combine, or the in-launch combine "c"), so
+        B * S * hs workgroups share the chip. ``kernels``: (variant, tag) pairs."""
+        s, B, i = g.s, g.B, g.i
+        nc = -(-g.hid // 32)
+        hs_opts = [hs for hs in (2, 3, 4, 6) if hs <= nc and B * S * hs <= 512] if B <= 16 else []
+        if not hs_opts:
+            return
+        if not hasattr(g, "part"):
+            g.part = g.buf(f"b{i}_part", max(hs_opts) * B * g.h * g.w * s.cout, dtype=torch.float32)
+        # per-span arrival tickets of the in-launch combine ("...c" variants)
+        cnt = g.buf(f"b{i}_cnt{S}", B * S, dtype=torch.int32)
+        for hs in hs_opts:
+            for v, tag in kernels:
+                for inl in (False, True):
+                    stream(f"stream{S}{tag}h{hs}" + ("c" if inl else ""), tab, v, hsplit=hs,
+                           part=g.part, cnt=cnt if inl else None)
+
+    def _band_variants(self, g):
+        """``band*``: row-streaming bands, every input row expanded once into an on-chip fp16 row."""
+        s, blk, B, OH, OW = g.s, g.blk, g.B, g.OH, g.OW
+        if not (blk["expand"] is not None and
+                FB.band_supported(s.cin, g.hid, s.cout, s.stride, s.dilation, OW)):
+            return []
+        bp_ = self._packed(blk, "band")
+        out = []
+        # (split 2 -- blocks 1-2 as two column bands, 5+5 waves with hs 2 -- measured
+        # 86-92 us vs 65-69 us for the full-width band: profiles/r3_negative_results.txt)
+        for split in (1,):
+            if not FB.band_supported(s.cin, g.hid, s.cout, s.stride, s.dilation, OW, split):
+                continue
+            for hs in ((1, 2) if FB.band_waves(OW, split) <= 8 else (1,)):
+                for nslot in (2, 1):
+                    if FB.band_lds(bp_, s.stride, OW, nslot, hs, split) > 160 * 1024:
                         continue
-                    for R in self._slice_rows(B, OH, nbx):
-                        variants.insert(0, (f"slice{R}w{nw}" + ("o" if oneb else ""), [
-                            lambda *_, x=inp, out=out, h=h, w=w, R=R, nw=nw, bp_=bp_, oneb=oneb: FB.fused_ir_slice(
-                                x, bp_, out, B=B, IH=h, IW=w, stride=s.stride, residual=s.residual,
-                                R=R, nw=nw, one_barrier=oneb)]))
-        outer_ops.append(Choice(f"block{i}", variants))
-        return out, OH, OW, s.cout
+                    # rows per band: grids of ~1-4 workgroups per CU slot (2 per CU x 256 CUs);
+                    # fewer rows re-expand more halo rows, more rows fill fewer CUs
+                    for R in _rows_per_band(B * OH, OH, (256, 512, 1024)):
+                        tag = f"band{R}s{nslot}" + ("h" if hs == 2 else "") + ("c" if split == 2 else "")
+                        out.append((tag, [
+                            lambda *_, R=R, nslot=nslot, hs=hs, split=split: FB.fused_ir_band(
+                                g.x, bp_, g.out, B=B, IH=g.h, IW=g.w, stride=s.stride,
+                                residual=s.residual, R=R, nslot=nslot, hs=hs, split=split)]))
+        return out[::-1]  # the last one built is listed first (fixed order: _mnv2_block)
 
-    @staticmethod
-    def _slice_rows(B: int, OH: int, nbx: int) -> List[int]:
-        """Rows per band for fused_ir_slice (one 12-15-wave workgroup per CU): grids of
-        ~1, 2, 3 and 4 workgroups per CU (256 CUs)."""
+    def _slice_variants(self, g):
+        """``slice*``: hidden-sliced row streaming, wave = column group x 32 hidden channels,
+        the chunk's weights in VGPRs (fused_ir_slice.hip: the band kernel's LDS weight
+        re-reads were its bottleneck)."""
+        s, blk, B, OH, OW = g.s, g.blk, g.B, g.OH, g.OW
+        if blk["expand"] is None:
+            return []
         out = []
-        for target in (256, 512, 768, 1024):
-            R = min(max(2, -(-B * nbx * OH // target)), OH)
-            if R not in out:
-                out.append(R)
-        return out
+        for nw in FB.slice_widths(s.cin, g.hid, s.cout, s.stride, s.dilation):
+            bp_ = self._packed(blk, "band")
+            twmax = 16 * nw - (2 if s.stride == 1 else 1)
+            nbx = -(-OW // twmax)
+            for oneb in (False, True):  # "o": one barrier per input row
+                if FB.slice_lds(bp_, s.stride, OW, nw, oneb) > 160 * 1024:
+                    continue
+                # rows per band (one 12-15-wave workgroup per CU): grids of ~1, 2, 3 and 4
+                # workgroups per CU (256 CUs)
+                for R in _rows_per_band(B * nbx * OH, OH, (256, 512, 768, 1024)):
+                    out.append((f"slice{R}w{nw}" + ("o" if oneb else ""), [
+                        lambda *_, R=R, nw=nw, bp_=bp_, oneb=oneb: FB.fused_ir_slice(
+                            g.x, bp_, g.out, B=B, IH=g.h, IW=g.w, stride=s.stride,
+                            residual=s.residual, R=R, nw=nw, one_barrier=oneb)]))
+        return out[::-1]  # the last one built is listed first (fixed order: _mnv2_block)
 
-    def _pack_band(self, blk: dict, s) -> dict:
-        m = blk["module"]
-        ew, eb = m.expand.fold()
-        dwf, dbf = m.dw.fold()
-        pwf, pbf = m.project.fold()
-        return FB.pack_fused_band(ew[:, :, 0, 0], eb, dwf[:, 0], dbf, pwf[:, :, 0, 0], pbf, Cin=s.cin,
-                                  hid=s.hidden, Cout=s.cout, device=self.device)
-
-    @staticmethod
-    def _band_rows(B: int, OH: int, OW: int, stride: int) -> List[int]:
-        """Rows per band for fused_ir_band (full-width bands): grids of ~1-4 workgroups
-        per CU slot (2 per CU x 256 CUs); fewer rows re-expand more halo rows, more rows
-        fill fewer CUs."""
-        out = []
-        for target in (256, 512, 1024):
-            R = min(max(2, -(-B * OH // target)), OH)
-            if R not in out:
-                out.append(R)
-        return out
+    def _packed(self, blk: dict, key: str) -> dict:
+        """The block's weights in the "span" / "band" kernels' layout, packed on first use."""
+        if key not in blk:
+            s, pack = blk["spec"], FS.pack_fused_span if key == "span" else FB.pack_fused_band
+            blk[key] = pack(*_fold_block(blk["module"]), Cin=s.cin, hid=s.hidden, Cout=s.cout,
+                            device=self.device)
+        return blk[key]
 
     @staticmethod
     def _span_counts(B: int, h: int, w: int) -> List[int]:
         """Spans per image for the fused span kernel: the smallest count whose spans fit
         the kernel's 144 pixels, and 2x / 4x that for small batches (more workgroups)."""
         s0 = -(-h * w // (FS.MAX_GROUPS * 16))
-        out = [s0, 2 * s0]
-        if B * s0 < 256:
-            out.append(4 * s0)
-        return out
+        return [s0, 2 * s0] + ([4 * s0] if B * s0 < 256 else [])
 
     def _span_table(self, h: int, w: int, S: int, dil: int, lattice: bool = False):
         key = (h, w, S, dil, lattice)
@@ -853,70 +652,32 @@ class HipDeepLab:
             self._span_tables[key] = (FS.lattice_table if lattice else FS.span_table)(h, w, S, dil, self.device)
         return self._span_tables[key]
 
-    def _pack_span(self, blk: dict, s) -> dict:
-        m = blk["module"]
-        ew, eb = m.expand.fold()
-        dwf, dbf = m.dw.fold()
-        pwf, pbf = m.project.fold()
-        return FS.pack_fused_span(ew[:, :, 0, 0], eb, dwf[:, 0], dbf, pwf[:, :, 0, 0], pbf, Cin=s.cin,
-                                  hid=s.hidden, Cout=s.cout, device=self.device)
-
-    def _resnet_block(self, ops, buf, i, blk, x, B, h, w, c):
+    # ------------------------------------------------------------ ResNet block
+    def _resnet_block(self, buf, i, blk, B, x, h, w, c):
         m = blk["blk"]
-        width = m.conv1.cout
-        cout = m.conv3.cout
+        width, cout = m.conv1.cout, m.conv3.cout
+        ops: List[Callable] = []
         w1, b1 = blk["conv1"]
         t1 = buf(f"r{i}_c1", B, h, w, width)
-        ops.append(lambda *_, x=x, t1=t1, h=h, w=w, c=c: K.conv_gemm(
+        ops.append(lambda *_: K.conv_gemm(
             x, w1, b1, t1, B=B, IH=h, IW=w, Cin=c, OH=h, OW=w, Cout=width, k=1, act="relu"))
         OH, OW = conv_out_hw(h, w, 3, m.stride, m.dilation)
         w2, b2 = blk["conv2"]
         t2 = buf(f"r{i}_c2", B, OH, OW, width)
-        ops.append(lambda *_, t1=t1, t2=t2, h=h, w=w, OH=OH, OW=OW: K.conv_gemm(
+        ops.append(lambda *_: K.conv_gemm(
             t1, w2, b2, t2, B=B, IH=h, IW=w, Cin=width, OH=OH, OW=OW, Cout=width, k=3,
             stride=m.stride, dil=m.dilation, act="relu"))
         if blk["down"] is not None:
             wd, bd = blk["down"]
             idt = buf(f"r{i}_down", B, OH, OW, cout)
-            ops.append(lambda *_, x=x, idt=idt, h=h, w=w, c=c, OH=OH, OW=OW: K.conv_gemm(
+            ops.append(lambda *_: K.conv_gemm(
                 x, wd, bd, idt, B=B, IH=h, IW=w, Cin=c, OH=OH, OW=OW, Cout=cout, k=1,
                 stride=m.stride, act=None))
         else:
             idt = x
         w3, b3 = blk["conv3"]
         out = buf(f"r{i}_out", B, OH, OW, cout)
-        ops.append(lambda *_, t2=t2, out=out, idt=idt, OH=OH, OW=OW: K.conv_gemm(
+        ops.append(lambda *_: K.conv_gemm(
             t2, w3, b3, out, B=B, IH=OH, IW=OW, Cin=width, OH=OH, OW=OW, Cout=cout, k=1,
             act="relu", res=idt))
-        return out, OH, OW, cout
-
-    # ------------------------------------------------------------------ run
-    def segment(self, frames: torch.Tensor, lut_x: torch.Tensor, lut_y: torch.Tensor,
-                out: Optional[torch.Tensor] = None, part: int = 0) -> torch.Tensor:
-        """frames: (B, Hc, Wc, 3) uint8 BGR on device -> (B, H, W) uint8 labels (static
-        buffer, or ``out``). ``part``: which independent copy of the plan to run (the
-        engine's concurrent half-batches use parts 0 and 1)."""
-        B, Hc, Wc, _ = frames.shape
-        if lut_x.numel() != self.W or lut_y.numel() != self.H:
-            raise ValueError("letterbox LUTs do not match the model input size")
-        ops, bufs = self._plan(B, Hc, Wc, part)
-        if out is not None and (out.shape != bufs["labels"].shape or out.dtype != torch.uint8
-                                or not out.is_contiguous() or out.device != bufs["labels"].device):
-            raise ValueError("segment: out must match the (B, H, W) uint8 label buffer")
-        frames = frames.contiguous()
-        self._labels_out = out
-        try:
-            for op in ops:
-                op(frames, lut_x, lut_y)
-        finally:
-            self._labels_out = None
-        return bufs["labels"] if out is None else out
-
-    def logits(self, frames, lut_x, lut_y) -> torch.Tensor:
-        """Run and return the NHWC logits buffer (tests)."""
-        self.segment(frames, lut_x, lut_y)
-        B, Hc, Wc, _ = frames.shape
-        return self._plans[(B, Hc, Wc)][1]["logits"][..., : self.num_classes]
-
-    def buffers(self, B: int, Hc: int, Wc: int) -> Dict[str, torch.Tensor]:
-        return self._plan(B, Hc, Wc)[1]
+        return ops, (out, OH, OW, cout)

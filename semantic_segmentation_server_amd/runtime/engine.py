@@ -254,10 +254,10 @@ class Engine:
         # concurrent plan copies gave rare label-map mismatches; round 3 traced those to
         # packed-f32 VALU results corrupted under co-residence (profiles/r3_packed_f32_race.txt)
         # and builds without them: 0 / 900 and 0 / 300 (headline shape) concurrent mismatches.
-        # (needs plan copies: the MobileNetV2 HIP model; the int8 / torch paths keep one
-        # plan, so their slots stay on the caller's stream)
+        # (needs plan copies: the bf16 and int8 HIP models (models/plan.py); the torch path
+        # has no plan, so its slots stay on the caller's stream)
         self.slot_parallel = (os.environ.get("SSA_SLOT_PARALLEL", "1") == "1" and self._split
-                              and hasattr(getattr(self, "_hip_model", None), "_labels_out"))
+                              and self._hip_model is not None)
         self.slot_streams: List[torch.cuda.Stream] = []
         self._slot_ev: List[tuple] = []  # per slot: (fork, ready) events, reused every step
         self.device_index = (self.device.index if self.device.index is not None
@@ -294,7 +294,7 @@ class Engine:
             torch.cuda.current_stream(self.device).wait_stream(s)
             if getattr(self, "_split", False):
                 lab = torch.empty((b.shape[0], self.H, self.W), dtype=torch.uint8, device=self.device)
-                hm = self._hip_model if hasattr(self._hip_model, "_labels_out") else None
+                hm = self._hip_model
                 B = b.shape[0]
                 P = self.model_parts if hm is not None and not self.slot_parallel else 1
                 P = P if P > 1 and B % P == 0 and B >= 2 * P else 1
@@ -353,7 +353,7 @@ class Engine:
         29.2k vs 28.3k / 28.0k frames/s at lag 1; batch 1 0.236 vs 0.351 ms per frame
         (profiles/r2_lag_ab.txt). Otherwise 1."""
         ok = (self.is_cuda and self.cfg.graph and self._use_device_post()
-              and hasattr(self._hip_model, "_labels_out")
+              and self._hip_model is not None
               and os.environ.get("SSA_SPLIT_POST", "1") != "0"
               and os.environ.get("SSA_SLOT_PARALLEL", "1") == "1"
               and os.environ.get("SSA_H2D_ON_SLOT", "1") == "1")

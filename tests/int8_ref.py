@@ -237,7 +237,7 @@ def check_plan(hm, ops, bufs, frames, lut_x, lut_y, *, run: bool = True, every_v
     ASPP branches not dead), so a failure cannot hide behind a clamp.
 
     Returns [(buffer, variant, share of codes off, max step)] for the int8 steps."""
-    from semantic_segmentation_server_amd.models.hip_model import Choice
+    from semantic_segmentation_server_amd.models.plan import Choice
 
     steps = plan_steps(hm)
     assert len(ops) == len(steps), (len(ops), len(steps))
