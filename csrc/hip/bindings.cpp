@@ -415,6 +415,23 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("palette"), py::arg("thr"), py::arg("min_area"), py::arg("num_bins"), py::arg("K"),
         py::arg("ws"), py::arg("records"), py::arg("stream"), py::arg("accum") = 0);
 
+  m.def("mask_rle_workspace_bytes", &mask_rle_workspace_bytes);
+  m.def("mask_rle",
+        [](uintptr_t labels, int B, int H, int W, int crop_h, int crop_w, int cap, uintptr_t out,
+           uintptr_t ws, uintptr_t stream) {
+          MaskRleParams p;
+          p.labels = P<const uint8_t>(labels); p.B = B; p.H = H; p.W = W;
+          p.crop_h = crop_h; p.crop_w = crop_w; p.cap = cap;
+          p.out = P<uint32_t>(out); p.ws = P<uint32_t>(ws);
+          mask_rle(p, S(stream));
+        },
+        py::arg("labels"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("crop_h"),
+        py::arg("crop_w"), py::arg("cap"), py::arg("out"), py::arg("ws"), py::arg("stream"));
+  m.def("mask_rle_copy_used", [](uintptr_t src, uintptr_t dst, int B, int cap, uintptr_t stream) {
+    mask_rle_copy_used(P<const uint32_t>(src), P<uint32_t>(dst), B, cap, S(stream));
+  });
+  m.attr("MASK_RLE_CHUNK") = mask_rle_chunk();
+
   m.attr("ACT_NONE") = (int)ACT_NONE;
   m.attr("ACT_RELU") = (int)ACT_RELU;
   m.attr("ACT_RELU6") = (int)ACT_RELU6;

@@ -310,4 +310,22 @@ void pack_rows(void* dst, const void* a, int a_words, const void* b, int b_words
 
 void postprocess(const PostParams& p, hipStream_t s);
 
+// ---- label-mask run-length encoder (mask_rle.hip) ---------------------------
+// Per frame, labels[:crop_h, :crop_w] as one flat row-major sequence of N = crop_h *
+// crop_w pixels (N < 2^24) -> out[b] = uint32[4 + cap]: n_runs (true total, may exceed
+// cap), N, crop_w, crop_h, then (label << 24) | start for the first min(n_runs, cap) runs
+// in run order. Words past those are not written.
+struct MaskRleParams {
+  const uint8_t* labels = nullptr;  // [B, H, W] (row stride W)
+  int B = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, cap = 0;
+  uint32_t* out = nullptr;          // [B, 4 + cap]
+  uint32_t* ws = nullptr;           // mask_rle_workspace_bytes(B, crop_h, crop_w)
+};
+size_t mask_rle_workspace_bytes(int B, int crop_h, int crop_w);
+int mask_rle_chunk();  // flat pixels per workgroup
+void mask_rle(const MaskRleParams& p, hipStream_t s);
+// src [B, 4 + cap] (mask_rle's out) -> dst, the same layout in pinned host memory: per frame
+// only the 4 + min(n_runs, cap) used words are written, by a kernel on stream s.
+void mask_rle_copy_used(const uint32_t* src, uint32_t* dst, int B, int cap, hipStream_t s);
+
 }  // namespace ssa

@@ -128,6 +128,25 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "world_size", 3, F.TYPE_INT32)
     _field(m, "detail", 4, F.TYPE_STRING)
 
+    m = fd.message_type.add(); m.name = "MaskRequest"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+
+    # the stream's latest label mask, run-length encoded over the flat row-major crop
+    # region (postprocess/mask_rle.py): run k covers run_lengths[k] pixels of class
+    # run_labels[k]; the lengths sum to width * height unless truncated
+    m = fd.message_type.add(); m.name = "SegmentationMask"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "frame_id", 2, F.TYPE_INT64)
+    _field(m, "timestamp", 3, F.TYPE_DOUBLE)
+    _field(m, "width", 4, F.TYPE_INT32)    # crop region, model-resolution pixels
+    _field(m, "height", 5, F.TYPE_INT32)
+    _field(m, "model_width", 6, F.TYPE_INT32)
+    _field(m, "model_height", 7, F.TYPE_INT32)
+    _field(m, "run_labels", 8, F.TYPE_BYTES)  # one class id per run
+    _field(m, "run_lengths", 9, F.TYPE_UINT32, F.LABEL_REPEATED)  # packed (proto3)
+    _field(m, "truncated", 10, F.TYPE_BOOL)
+    _field(m, "total_runs", 11, F.TYPE_UINT32)
+
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"
     E = ".sem_seg_server.Empty"
@@ -135,6 +154,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _method(svc, "ListStreams", E, P + "StreamList")
     _method(svc, "GetStats", E, P + "Stats")
     _method(svc, "Health", E, P + "HealthStatus")
+    _method(svc, "GetSegmentationMask", P + "MaskRequest", P + "SegmentationMask")
     return fd
 
 
@@ -189,6 +209,8 @@ StreamInfo = _cls("sem_seg_server.v2.StreamInfo")
 StreamList = _cls("sem_seg_server.v2.StreamList")
 Stats = _cls("sem_seg_server.v2.Stats")
 HealthStatus = _cls("sem_seg_server.v2.HealthStatus")
+MaskRequest = _cls("sem_seg_server.v2.MaskRequest")
+SegmentationMask = _cls("sem_seg_server.v2.SegmentationMask")
 
 # ---- grpc.health.v1 ---------------------------------------------------------
 HealthCheckRequest = _cls("grpc.health.v1.HealthCheckRequest")
@@ -203,6 +225,7 @@ V2_METHODS = {
     "ListStreams": (Empty, StreamList),
     "GetStats": (Empty, Stats),
     "Health": (Empty, HealthStatus),
+    "GetSegmentationMask": (MaskRequest, SegmentationMask),
 }
 
 

@@ -71,8 +71,11 @@ class SemanticSegmentationV2Servicer:
 
     def __init__(self, hub: ResultHub, labels: Dict[int, str], num_detections: int = 3,
                  streams: Optional[list] = None, metrics=None,
-                 health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None):
+                 health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None, *,
+                 serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0)):
         self.hub = hub
+        self.serve_masks = bool(serve_masks)  # --serve_masks: GetSegmentationMask is enabled
+        self.model_size = model_size          # (width, height) of the label maps
         self.labels = labels
         self.num_detections = int(num_detections)
         self.streams = streams or []
@@ -94,6 +97,31 @@ class SemanticSegmentationV2Servicer:
         if request.pad:
             data.extend(P.TaggedObject(stream_id=request.stream_id) for _ in range(n - len(data)))
         return P.StreamSegmentedObjects(data=data)
+
+    def GetSegmentationMask(self, request, context):
+        """The stream's latest label mask. The producer stores run starts; the lengths of
+        the wire format are taken here, for the one mask an RPC asks for."""
+        from ..postprocess import mask_rle as MR
+        stream = int(request.stream_id)
+        if not self.serve_masks:
+            context.set_code(grpc.StatusCode.FAILED_PRECONDITION)
+            context.set_details("label masks are not enabled (start the server with --serve_masks)")
+            return P.SegmentationMask()
+        if self.hub.get(stream) is None:
+            context.set_code(grpc.StatusCode.NOT_FOUND)
+            context.set_details(f"unknown stream_id {request.stream_id}")
+            return P.SegmentationMask()
+        m = self.hub.mask(stream)
+        if m is None:
+            context.set_code(grpc.StatusCode.UNAVAILABLE)
+            context.set_details(f"no frame of stream {stream} collected yet")
+            return P.SegmentationMask()
+        labs, lens, truncated, total = MR.to_wire(m.words)
+        return P.SegmentationMask(
+            stream_id=stream, frame_id=m.frame_id, timestamp=m.ts, width=int(m.words[2]),
+            height=int(m.words[3]), model_width=int(self.model_size[0]),
+            model_height=int(self.model_size[1]), run_labels=labs, run_lengths=lens.tolist(),
+            truncated=truncated, total_runs=total)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

@@ -72,13 +72,52 @@ def rpc_latency(target: str, n: int = 2000, warmup: int = 200) -> Dict[str, floa
             "mean_ms": float(a.mean()), "n": n}
 
 
+def fetch_mask(target: str, stream: int = 0):
+    """(SegmentationMask message, decoded uint8 [height, width] label map; pixels a truncated
+    mask does not cover are 255) of the stream's latest frame (v2 GetSegmentationMask)."""
+    from .postprocess import mask_rle
+    with grpc.insecure_channel(target) as ch:
+        m = SemanticSegmentationV2Stub(ch).GetSegmentationMask(P.MaskRequest(stream_id=stream))
+    return m, mask_rle.from_wire(m.run_labels, m.run_lengths, m.width, m.height,
+                                 allow_truncated=m.truncated)
+
+
+def print_mask(m, lab: np.ndarray, labels: Dict[int, str]) -> None:
+    from .labels import label_name
+    print("stream {} frame {} ts {:.3f}: mask {} x {} (model {} x {}), {} runs{}".format(
+        m.stream_id, m.frame_id, m.timestamp, m.width, m.height, m.model_width, m.model_height,
+        m.total_runs, " (truncated to {})".format(len(m.run_labels)) if m.truncated else ""))
+    ids, counts = np.unique(lab, return_counts=True)
+    for i, c in sorted(zip(ids.tolist(), counts.tolist()), key=lambda t: -t[1]):
+        name = "(not covered)" if m.truncated and i == 255 else label_name(labels, i)
+        print("  {:>3} {:<20} {:>8} px  {:5.1f} %".format(i, name, c, 100.0 * c / lab.size))
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="sem_seg_server example client")
     p.add_argument("--target", default="localhost:50051")
     p.add_argument("--count", type=int, default=None)
     p.add_argument("--latency", action="store_true", help="measure GetSegmentedObjects latency")
     p.add_argument("--stats", action="store_true", help="print v2 GetStats")
+    p.add_argument("--mask", nargs="?", type=int, const=0, default=None, metavar="STREAM",
+                   help="fetch the stream's latest label mask (server run with --serve_masks), "
+                        "decode it and print per-class pixel counts")
+    p.add_argument("--mask_out", default=None, metavar="PATH.npy",
+                   help="with --mask: save the decoded uint8 label map")
+    p.add_argument("--labels", default=None, help="label file for --mask (default: Pascal VOC)")
     a = p.parse_args(argv)
+    if a.mask is not None:
+        from .labels import PASCAL_LABELS, load_labels
+        try:
+            m, lab = fetch_mask(a.target, a.mask)
+        except grpc.RpcError as err:
+            print(err.details())
+            print("{}, {}".format(err.code().name, err.code().value))
+            return 1
+        print_mask(m, lab, load_labels(a.labels or PASCAL_LABELS))
+        if a.mask_out:
+            np.save(a.mask_out, lab)
+        return 0
     if a.latency:
         print(rpc_latency(a.target))
         return 0

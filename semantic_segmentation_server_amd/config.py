@@ -57,6 +57,8 @@ class Config:
     graph: bool = True                     # hipGraph capture of the per-step device work
     contour_mode: str = "fast"             # fast (device CCL stats) | exact (host tracer)
     max_segments: int = 64                 # per-frame record capacity on device
+    serve_masks: bool = False              # run-length encode every label map (v2 GetSegmentationMask)
+    mask_max_runs: int = 32768             # run slots per frame; more runs truncate the mask
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -128,6 +130,12 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.set_defaults(graph=d.graph)
     p.add_argument("--contour_mode", choices=["fast", "exact"], default=d.contour_mode)
     p.add_argument("--max_segments", type=int, default=d.max_segments)
+    p.add_argument("--serve_masks", action="store_true",
+                   help="run-length encode every frame's label map on the device and serve the "
+                        "latest one per stream (v2 GetSegmentationMask); one GPU per process group")
+    p.add_argument("--mask_max_runs", type=int, default=d.mask_max_runs,
+                   help="run slots per frame of the mask encoder; a frame with more runs is "
+                        "served truncated")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

@@ -1105,6 +1105,62 @@ def postprocess(labels, palette, ws, records, *, B, H, W, crop_h, crop_w, min_ar
     return records
 
 
+MASK_RLE_CHUNK = 4096  # flat pixels per workgroup of mask_rle (the module's MASK_RLE_CHUNK)
+MASK_RLE_MAX_PIXELS = 1 << 24  # a run start is stored in 24 bits
+
+
+def mask_rle_workspace_bytes(B, crop_h, crop_w) -> int:
+    return int(_hip_mod().mask_rle_workspace_bytes(B, crop_h, crop_w))
+
+
+def mask_rle(labels, out, ws, *, B, H, W, crop_h, crop_w, cap):
+    """Run-length encode ``labels[:, :crop_h, :crop_w]`` (csrc/hip/mask_rle.hip; the format
+    is postprocess/mask_rle.py's): per frame ``out[b] = [n_runs, N, crop_w, crop_h,
+    (label << 24) | start ...]`` with the first ``min(n_runs, cap)`` runs in run order.
+    ``out``: uint32/int32 [B, 4 + cap]; ``ws``: at least ``mask_rle_workspace_bytes``."""
+    _chk(labels, torch.uint8, "labels", B * H * W)
+    if out.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f"out: expected uint32 or int32, got {out.dtype}")
+    _chk(out, out.dtype, "out")
+    if cap < 2:
+        raise ValueError(f"mask_rle: cap {cap} < 2")
+    if B < 1 or B > 65535:
+        raise ValueError(f"mask_rle: bad batch {B}")
+    if tuple(out.shape) != (B, 4 + cap):
+        raise ValueError(f"out: shape {tuple(out.shape)} != ({B}, {4 + cap})")
+    if not (1 <= crop_h <= H and 1 <= crop_w <= W):
+        raise ValueError(f"mask_rle: crop {crop_h} x {crop_w} outside the {H} x {W} map")
+    if crop_h * crop_w >= MASK_RLE_MAX_PIXELS:
+        raise ValueError(f"mask_rle: {crop_h} x {crop_w} pixels do not fit 24-bit run starts")
+    m = _hip_mod()
+    if m.MASK_RLE_CHUNK != MASK_RLE_CHUNK:
+        raise RuntimeError("mask_rle: MASK_RLE_CHUNK differs from the built module's")
+    _chk(ws, torch.uint8, "ws", mask_rle_workspace_bytes(B, crop_h, crop_w))
+    m.mask_rle(_ptr(labels), B, H, W, crop_h, crop_w, cap, _ptr(out), _ptr(ws), _stream())
+    _dbg('mask_rle')
+    return out
+
+
+def mask_rle_copy_to_host(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """``mask_rle``'s ``out`` ([B, 4 + cap] uint32/int32, contiguous, on the device) -> ``dst``
+    (the same shape and dtype in PINNED host memory) by a kernel on the current stream, like
+    ``copy_to_host`` -- but per frame only the ``4 + min(n_runs, cap)`` used words cross the
+    bus; the rest of ``dst`` keeps what it held."""
+    if not src.is_cuda or dst.is_cuda or not dst.is_pinned():
+        raise ValueError("mask_rle_copy_to_host: CUDA source, pinned host destination")
+    if src.dtype not in (torch.int32, torch.uint32) or dst.dtype != src.dtype:
+        raise TypeError("mask_rle_copy_to_host: uint32 or int32 tensors of one dtype required")
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise ValueError("mask_rle_copy_to_host: contiguous tensors required")
+    if src.dim() != 2 or src.shape[1] < 4 + 2 or tuple(dst.shape) != tuple(src.shape):
+        raise ValueError(f"mask_rle_copy_to_host: shapes {tuple(src.shape)} -> {tuple(dst.shape)}")
+    if not 1 <= src.shape[0] <= 65535:
+        raise ValueError(f"mask_rle_copy_to_host: bad batch {src.shape[0]}")
+    _hip_mod().mask_rle_copy_used(src.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1] - 4,
+                                  _stream())
+    return dst
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

@@ -173,6 +173,14 @@ class DataParallelPipeline:
         if gather not in ("host", "rccl"):
             raise ValueError("gather must be 'auto', 'host' or 'rccl'")
         self.ctx = ctx
+        # --serve_masks: the engine run-length encodes every label map; each step's run words
+        # travel to a pinned buffer with (and like) that step's records. One GPU only: the
+        # masks are not gathered across ranks
+        self.mask_cap = int(getattr(engine, "mask_cap", 0) or 0)
+        if self.mask_cap and ctx.initialized and ctx.world > 1:
+            raise ValueError("serve_masks is not supported in a multi-rank group (world size "
+                             f"{ctx.world}): label masks are not gathered across ranks; run one "
+                             "GPU, or the supervised server (independent workers)")
         # lag L >= 1: step k collects step k-L's records, with L + 1 staging slots (so L + 1
         # steps can be in flight on a slot-parallel engine); SSA_PIPE_LAG overrides a
         # non-zero lag, else the engine may ask for more depth (slot-parallel: 2)
@@ -246,6 +254,9 @@ class DataParallelPipeline:
         self.local_rec = [torch.empty((self.B, self.rec_width), dtype=torch.float32,
                                       pin_memory=self.cuda) for _ in range(NS)]
         self.local_meta = [torch.empty((self.B, 3), dtype=torch.float64) for _ in range(NS)]
+        self.local_mask = [torch.zeros((self.B, 4 + self.mask_cap), dtype=torch.int32,
+                                       pin_memory=self.cuda) for _ in range(NS)] \
+            if self.mask_cap else None
         if gather == "host" and ctx.initialized:
             self.host_send = torch.empty((self.B, self.comb_width), dtype=torch.float32)
             self.host_gather = torch.empty((ctx.world, self.B, self.comb_width), dtype=torch.float32)
@@ -465,7 +476,12 @@ class DataParallelPipeline:
             self._prefetch_next(next_frames)
         if packed is None:  # host post-processing path (torch backend / exact mode)
             self.frames_done += B * self.ctx.world
+            if self.mask_cap and self.hub is not None and hasattr(self.hub, "push_masks"):
+                self.hub.push_masks(self.engine.host_masks(labels), self._node_meta(fids, strm, tss))
             return self.engine.records_from_labels(labels, fids, tss, strm)
+        # the run words of this step's label maps: produced with the records (same graph,
+        # same stream), copied with them, before the step's event
+        mask = self.engine.mask_packed if self.mask_cap else None
         slot = self._rslot
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
@@ -476,10 +492,14 @@ class DataParallelPipeline:
             if rs is not None:
                 with fast_cuda.StreamSwitch(rs):
                     self._d2h(packed, self.local_rec[slot])
+                    if mask is not None:
+                        self._d2h_mask(mask, self.local_mask[slot])
                 ev = self._rec_ev[slot]  # per record slot: collected before the slot is reused
                 ev.record(rs)
             else:
                 self._d2h(packed, self.local_rec[slot])
+                if mask is not None:
+                    self._d2h_mask(mask, self.local_mask[slot])
                 if self.cuda:
                     ev = self._rec_ev[slot]
                     ev.record(fast_cuda.current_stream(self.dev_index))
@@ -505,6 +525,8 @@ class DataParallelPipeline:
             self.frames_done += B * self.ctx.world
             if self.ctx.is_root:
                 self._d2h(src, hdst)
+            if mask is not None:  # world size 1 (checked at construction)
+                self._d2h_mask(mask, self.local_mask[slot])
             # every rank (non-root ones too) records the step and goes through the lag
             # throttle: meta_host[slot] is rewritten only after the step that last used it
             # has been collected, i.e. after its H2D copy ran (VERDICT r3 Weak #4: non-root
@@ -538,6 +560,17 @@ class DataParallelPipeline:
                 and getattr(self.engine, "backend", "hip") == "hip":
             from ..ops import hip_ops
             hip_ops.copy_to_host(src, dst)
+        else:
+            dst.copy_(src, non_blocking=self.cuda)
+
+    def _d2h_mask(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+        """Run words -> pinned host buffer on the current stream, as ``_d2h``; the HIP build
+        copies only each frame's header and counted runs (the static buffer is sized for the
+        worst frame: 128 KiB per frame at the default capacity)."""
+        if self.cuda and src.is_cuda and dst.is_pinned() and src.is_contiguous() \
+                and getattr(self.engine, "backend", "hip") == "hip":
+            from ..ops import hip_ops
+            hip_ops.mask_rle_copy_to_host(src, dst)
         else:
             dst.copy_(src, non_blocking=self.cuda)
 
@@ -680,6 +713,7 @@ class DataParallelPipeline:
             self.records_out += len(recs)
             if self.hub is not None:
                 self.hub.push_records(recs, self._single_stream(meta))
+                self._push_masks(slot, meta)
             self._observe(meta)
             return recs
         if not self.ctx.is_root:
@@ -697,5 +731,12 @@ class DataParallelPipeline:
         self.records_out += len(recs)
         if self.hub is not None:
             self.hub.push_records(recs, self._single_stream(meta))
+            self._push_masks(slot, meta)
         self._observe(meta)
         return recs
+
+    def _push_masks(self, slot: int, meta: np.ndarray) -> None:
+        """Hand the collected step's run words (pinned, reused: the hub copies what it keeps)
+        and its frame metadata to the hub, if it takes masks."""
+        if self.mask_cap and hasattr(self.hub, "push_masks"):
+            self.hub.push_masks(self.local_mask[slot].numpy(), meta)

@@ -19,12 +19,18 @@ from ..runtime.results import RECORD_DTYPE
 
 class DevicePostprocess:
     def __init__(self, device: torch.device, H: int, W: int, palette: np.ndarray, K: int = 64,
-                 bins: int = 32, thr: int = 127):
+                 bins: int = 32, thr: int = 127, mask_cap: int = 0):
         self.device = device
+        # run slots per frame of the label-mask encoder (mask_rle.hip); 0: no encoder, no
+        # buffer, no launch
+        self.mask_cap = int(mask_cap)
+        self._mask_bufs: Dict[tuple, tuple] = {}
         self.H, self.W, self.K, self.bins, self.thr = H, W, K, bins, thr
         self.palette = torch.tensor(np.asarray(palette, np.int32).reshape(256, 3), device=device)
         self._bufs: Dict[int, tuple] = {}
         self._host: Dict[int, torch.Tensor] = {}
+        self._mask_host: Dict[int, torch.Tensor] = {}
+        self.last_mask = None
         # accumulation pass: pixel strips (0), LDS-staged 32 x 32 (1) or 64 x 64 (2) tiles;
         # unset: by batch size (accum_for)
         env = os.environ.get("SSA_POST_ACCUM")
@@ -47,11 +53,28 @@ class DevicePostprocess:
             self._bufs[B] = (ws, rec)
         return self._bufs[B]
 
+    def mask_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(workspace, [B, 4 + mask_cap] int32 run words) of the mask encoder for a batch of B
+        frames: static like the records buffer, shared by every slot, ordered by the stream
+        the post-processing runs on."""
+        key = (B, crop_w, crop_h)
+        if key not in self._mask_bufs:
+            from . import mask_rle as MR
+            MR.check_geometry(crop_w, crop_h, self.mask_cap)
+            ws = torch.zeros(max(4, hip_ops.mask_rle_workspace_bytes(B, crop_h, crop_w)),
+                             dtype=torch.uint8, device=self.device)
+            words = torch.zeros((B, 4 + self.mask_cap), dtype=torch.int32, device=self.device)
+            self._mask_bufs[key] = (ws, words)
+        return self._mask_bufs[key]
+
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
-            out: torch.Tensor = None) -> torch.Tensor:
+            out: torch.Tensor = None, mask_out: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
-        shared per B: runs that share it must be ordered on one stream."""
+        shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
+        the label maps are run-length encoded right after, on the same stream (so inside the
+        same captured graph), into ``mask_buffers(B)`` or ``mask_out`` ([B, 4 + mask_cap]
+        int32 rows); ``last_mask`` is the buffer written."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -64,6 +87,13 @@ class DevicePostprocess:
         hip_ops.postprocess(labels, self.palette, ws, rec, B=B, H=self.H, W=self.W, crop_h=crop_h,
                             crop_w=crop_w, min_area=min_area, K=self.K, bins=self.bins, thr=self.thr,
                             accum=self.accum_for(B))
+        if self.mask_cap:
+            mws, words = self.mask_buffers(B, crop_w, crop_h)
+            if mask_out is not None:
+                words = mask_out
+            hip_ops.mask_rle(labels, words, mws, B=B, H=self.H, W=self.W, crop_h=crop_h,
+                             crop_w=crop_w, cap=self.mask_cap)
+            self.last_mask = words
         return rec
 
     def fetch(self, rec: torch.Tensor, frame_ids: Sequence[int], ts: Sequence[float],
@@ -76,3 +106,13 @@ class DevicePostprocess:
         h.copy_(rec, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return unpack_records(h.numpy(), self.K, frame_ids, ts, streams)
+
+    def fetch_masks(self, words: torch.Tensor) -> np.ndarray:
+        """Synchronous D2H of the run words of ``run`` -> uint32 [B, 4 + mask_cap] (a copy)."""
+        B = words.shape[0]
+        h = self._mask_host.get(B)
+        if h is None:
+            h = self._mask_host[B] = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+        h.copy_(words, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return h.numpy().view(np.uint32).copy()

@@ -104,6 +104,16 @@ class Engine:
         self._static: Dict[str, torch.Tensor] = {}
         self._hip_model = None
         self._hip_post = None
+        # --serve_masks: run slots per frame of the label-mask encoder (0 = off: no kernel,
+        # no buffer). mask_packed: the [B, 4 + cap] int32 run words of the last run_device
+        # (device post-processing: a static device buffer ordered like the records; CPU: a
+        # host tensor); masks: the same of the last step(), uint32 on the host
+        self.mask_cap = int(cfg.mask_max_runs) if cfg.serve_masks else 0
+        if cfg.serve_masks:
+            from ..postprocess import mask_rle as MR
+            MR.check_geometry(self.W, self.H, self.mask_cap)  # every crop is within H x W
+        self.mask_packed: Optional[torch.Tensor] = None
+        self.masks: Optional[np.ndarray] = None
         if self.backend == "torch":
             self.model = self.model.to(self.device, self.dtype)
             if self.is_cuda:
@@ -163,23 +173,46 @@ class Engine:
             logits = self.model(x)
         return R.upsample_argmax(logits, self.H, self.W)
 
-    def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None):
+    def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
+                     mask_out: Optional[torch.Tensor] = None):
+        """Device records of ``labels`` and, with ``mask_cap``, their run-length masks
+        right after on the same stream (``mask_packed``): one captured graph holds both."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
             # per-root fill histograms are the largest part of the workspace
             self._hip_post = DevicePostprocess(self.device, self.H, self.W, self.palette,
                                                self.cfg.max_segments,
-                                               bins=max(1, min(256, self.cfg.num_classes)))
-        return self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out)
+                                               bins=max(1, min(256, self.cfg.num_classes)),
+                                               mask_cap=self.mask_cap)
+        rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
+                                 mask_out=mask_out)
+        if self.mask_cap:
+            self.mask_packed = self._hip_post.last_mask
+        return rec
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
+
+    def host_masks(self, labels) -> np.ndarray:
+        """uint32 [B, 4 + cap] run words of host label maps by the numpy definition
+        (postprocess/mask_rle.py): the CPU path, and a GPU without device post-processing."""
+        from ..postprocess import mask_rle as MR
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        out = np.zeros((lab.shape[0], 4 + self.mask_cap), np.uint32)
+        for b in range(lab.shape[0]):
+            MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
+        return out
 
     def _step_device(self, frames: torch.Tensor):
         labels = self._infer_eager(frames)
         if self._use_device_post():
             return labels, self._device_post(labels)
+        if self.mask_cap:
+            # no device post-processing: on the CPU the masks are encoded here; a GPU's host
+            # post-processing path encodes them where it brings the label maps to the host
+            self.mask_packed = None if self.is_cuda else \
+                torch.from_numpy(self.host_masks(labels).view(np.int32))
         if not self.is_cuda and self.cfg.contour_mode != "none":
             return labels, self._host_packed(labels)
         return labels, None
@@ -215,6 +248,7 @@ class Engine:
             labels, post = self._step_device(st["frames"])
         st["labels"] = labels
         st["post"] = post
+        st["mask"] = self.mask_packed
         self._graph = g
         self._graph_B = B
 
@@ -308,8 +342,11 @@ class Engine:
                         hm.segment(b[sl], self.lut_x, self.lut_y, out=lab[sl], part=part)
                     post = torch.zeros((B, 1 + 5 * self.cfg.max_segments), dtype=torch.float32,
                                        device=self.device)
-                    for sl in sls:  # warm-up outside capture
-                        self._device_post(lab[sl], out=post[sl])
+                    mask = torch.zeros((B, 4 + self.mask_cap), dtype=torch.int32,
+                                       device=self.device) if self.mask_cap else None
+                    msl = [mask[sl] if mask is not None else None for sl in sls]
+                    for sl, m_ in zip(sls, msl):  # warm-up outside capture
+                        self._device_post(lab[sl], out=post[sl], mask_out=m_)
                     torch.cuda.synchronize(self.device)
                     gm, gp = [], []
                     for part, sl in enumerate(sls):
@@ -319,7 +356,7 @@ class Engine:
                         gm.append(g_)
                         g_ = torch.cuda.CUDAGraph()
                         with torch.cuda.graph(g_):
-                            self._device_post(lab[sl], out=post[sl])
+                            self._device_post(lab[sl], out=post[sl], mask_out=msl[part])
                         gp.append(g_)
                     while len(self.model_streams) < P - 1:
                         self.model_streams.append(torch.cuda.Stream(self.device))
@@ -335,14 +372,15 @@ class Engine:
                         else:
                             lab.copy_(self._infer_eager(b))
                     gp = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gp):
+                    with torch.cuda.graph(gp):  # records, then (serve_masks) the run-length masks
                         post = self._device_post(lab)
-                ent = (tuple(frames.shape), gm, lab, post, gp, torch.cuda.Event())
+                    mask = self.mask_packed
+                ent = (tuple(frames.shape), gm, lab, post, gp, torch.cuda.Event(), mask)
             else:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     labels, post = self._step_device(b)
-                ent = (tuple(frames.shape), g, labels, post, None, None)
+                ent = (tuple(frames.shape), g, labels, post, None, None, self.mask_packed)
             self._bound_graphs[key] = ent
         return ent
 
@@ -378,7 +416,9 @@ class Engine:
         if self.cfg.graph and self.is_cuda:
             ent = self._bound_graph(frames)
             if ent is not None:
-                _, g, labels, post, gpost, post_done = ent
+                _, g, labels, post, gpost, post_done, mask = ent
+                if mask is not None:  # written by the replay below, like `post`
+                    self.mask_packed = mask
                 if gpost is None:
                     g.replay()
                     return labels, post
@@ -451,6 +491,8 @@ class Engine:
                 self._capture(B)
             self._static["frames"].copy_(frames, non_blocking=True)
             self._graph.replay()
+            if self.mask_cap:
+                self.mask_packed = self._static["mask"]
             return self._static["labels"], self._static["post"]
         return self._step_device(frames)
 
@@ -500,6 +542,8 @@ class Engine:
             if self.debug is not None and self.debug.want():
                 self.debug.dump(frames_host[0], labels[0].numpy(), self.crop_w, self.crop_h,
                                 _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))
+            if self.mask_cap:
+                self.masks = self.host_masks(labels)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         with torch.cuda.stream(self.stream):
@@ -512,9 +556,13 @@ class Engine:
                 with tr.stage("d2h+records", self.stream):
                     recs = self._hip_post.fetch(post, frame_ids, ts,
                                                 _per_frame(streams, len(frame_ids)), self.W, self.H)
+                if self.mask_cap:  # same stream, after the records: one more small D2H
+                    self.masks = self._hip_post.fetch_masks(self.mask_packed)
             else:
                 recs = None
         self.stream.synchronize()
+        if self.mask_cap and post is None:
+            self.masks = self.host_masks(labels)
         if self.debug is not None and self.debug.want():
             self.debug.dump(frames_host[0], labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

@@ -24,7 +24,7 @@ from __future__ import annotations
 
 import collections
 import threading
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Dict, Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -130,14 +130,22 @@ class ResultBuffer:
         return self._size
 
 
+class StoredMask(NamedTuple):
+    """A stream's latest label mask: the run words are the hub's own copy."""
+    frame_id: int
+    ts: float
+    words: np.ndarray  # uint32[4 + stored runs] (postprocess/mask_rle.py)
+
+
 class ResultHub:
-    """One ``ResultBuffer`` per stream id."""
+    """One ``ResultBuffer`` per stream id (and, with --serve_masks, its latest mask)."""
 
     def __init__(self, num_streams: int = 1, maxlen: Optional[int] = 4096):
         self.buffers: Dict[int, ResultBuffer] = {
             s: ResultBuffer(maxlen) for s in range(num_streams)}
         self.maxlen = maxlen
         self._lock = threading.Lock()
+        self._masks: Dict[int, StoredMask] = {}
 
     def get(self, stream: int) -> Optional[ResultBuffer]:
         """The stream's buffer, or None for a stream id the hub does not serve (RPC
@@ -169,6 +177,35 @@ class ResultHub:
         for s in np.unique(streams):
             sel = recs[streams == s]
             self.buffer(int(s)).push_frame(sel)
+
+    # ---- label masks (--serve_masks): the LATEST run-length mask per stream
+    def put_mask(self, stream: int, frame_id: int, ts: float, words: np.ndarray) -> None:
+        """Store a COPY of ``words`` (header + stored runs, postprocess/mask_rle.py) as the
+        stream's latest mask."""
+        m = StoredMask(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True))
+        with self._lock:
+            self._masks[int(stream)] = m
+
+    def push_masks(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """``rows``: [F, 4 + cap] run words of a collected batch (uint32, or int32 bits; e.g.
+        a pinned buffer the producer reuses); ``meta``: [F, 3] (frame id, stream, capture
+        ts) in the same order. Of several frames of one stream only the last is copied,
+        and only its ``4 + min(n_runs, cap)`` used words."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint32:
+            rows = rows.view(np.uint32)
+        cap = rows.shape[1] - 4
+        last: Dict[int, int] = {}
+        for i in range(len(rows)):
+            last[int(meta[i, 1])] = i
+        for st, i in last.items():
+            used = 4 + min(int(rows[i, 0]), cap)
+            self.put_mask(st, int(meta[i, 0]), float(meta[i, 2]), rows[i, :used])
+
+    def mask(self, stream: int) -> Optional["StoredMask"]:
+        """The stream's latest mask (frame_id, ts, words), or None before the first one."""
+        with self._lock:
+            return self._masks.get(int(stream))
 
     @property
     def depth(self) -> int:

@@ -22,6 +22,10 @@ inside a write cannot leave a lock held or half a message behind for its success
   memory (``_RecordRing``; no pickling, one memcpy per step on each side); the worker
   publishes a chunk by advancing the write index after the rows, the parent advances
   the read index after copying them out. A full ring drops the chunk (counted).
+* masks (``--serve_masks``): per stream, two slots of run words in a second shared-memory
+  block (``_MaskChannel``), each guarded by a sequence counter (odd while the worker
+  writes it); the parent copies the newest complete slot into its hub and keeps its
+  previous copy when it meets a slot being written.
 * progress: the ring header carries the worker's step count and the time of its last
   step, written by the worker's producer loop itself -- liveness is step PROGRESS, not a
   timer thread, so a worker whose GPU hangs (producer stuck in a synchronize) goes stale
@@ -167,17 +171,129 @@ class _RecordRing:
                 pass
 
 
-class _RingHub:
-    """The worker's stand-in for the ResultHub: pushes go to the shared-memory ring."""
+class _MaskChannel:
+    """The latest label mask per stream (postprocess/mask_rle.py run words) in POSIX shared
+    memory, single writer (the worker) / single reader (the parent).
 
-    def __init__(self, ring: _RecordRing):
+    Block header (int64): 0 streams, 1 cap, 2 first (global) stream id. Per stream two
+    slots, each [int64 seq, int64 frame id, float64 ts, int64 pad | uint32[4 + cap]]. The
+    writer alternates a stream's slots: it sets the slot's seq to the odd 2k + 1, writes
+    the payload, then the even 2k + 2 (k: the stream's write count; x86-64 keeps stores in
+    program order). The reader takes a slot only if its seq is even, newer than the last
+    one it delivered and unchanged after the copy; otherwise it keeps its previous copy and
+    looks again at the next pull. With two slots the writer never touches the newest
+    complete mask, so the reader always finds one."""
+
+    HDR = 4
+
+    def __init__(self, streams: int = 1, cap: int = 2, first: int = 0, name: Optional[str] = None):
+        self.owner = name is None
+        if self.owner:
+            nbytes = self.HDR * 8 + int(streams) * 2 * self._slot_bytes(int(cap))
+            self.shm = shared_memory.SharedMemory(create=True, size=nbytes)
+        else:
+            self.shm = shared_memory.SharedMemory(name=name)
+        buf = self.shm.buf
+        self.hdr = np.ndarray((self.HDR,), dtype=np.int64, buffer=buf)
+        if self.owner:
+            np.ndarray((nbytes,), dtype=np.uint8, buffer=buf)[:] = 0
+            self.hdr[0], self.hdr[1], self.hdr[2] = streams, cap, first
+        self.S, self.cap, self.first = int(self.hdr[0]), int(self.hdr[1]), int(self.hdr[2])
+        sb = self._slot_bytes(self.cap)
+        self.meta, self.ts, self.words = [], [], []
+        for i in range(self.S * 2):
+            off = self.HDR * 8 + i * sb
+            self.meta.append(np.ndarray((4,), dtype=np.int64, buffer=buf, offset=off))
+            self.ts.append(np.ndarray((1,), dtype=np.float64, buffer=buf, offset=off + 16))
+            self.words.append(np.ndarray((4 + self.cap,), dtype=np.uint32, buffer=buf, offset=off + 32))
+        self._writes = [0] * self.S      # worker side: writes per stream
+        self._delivered = [0] * self.S   # parent side: seq of the last mask taken per stream
+
+    @staticmethod
+    def _slot_bytes(cap: int) -> int:
+        return 32 + (4 * (4 + cap) + 7) // 8 * 8
+
+    @property
+    def name(self) -> str:
+        return self.shm.name
+
+    # ---- worker side
+    def write(self, stream: int, frame_id: int, ts: float, words: np.ndarray) -> None:
+        s = int(stream) - self.first
+        if not 0 <= s < self.S or len(words) > 4 + self.cap:
+            return
+        k = self._writes[s]
+        i = 2 * s + (k & 1)
+        self.meta[i][0] = 2 * k + 1
+        self.meta[i][1] = int(frame_id)
+        self.ts[i][0] = float(ts)
+        self.words[i][:len(words)] = words
+        self.meta[i][0] = 2 * k + 2
+        self._writes[s] = k + 1
+
+    # ---- parent side
+    def pull(self) -> list:
+        """[(stream, frame_id, ts, words copy)] of the masks completed since the last pull
+        (the newest per stream)."""
+        out = []
+        for s in range(self.S):
+            best = None
+            for i in (2 * s, 2 * s + 1):
+                seq = int(self.meta[i][0])
+                if seq & 1 or seq <= self._delivered[s] or (best is not None and seq < best[0]):
+                    continue
+                fid, ts = int(self.meta[i][1]), float(self.ts[i][0])
+                used = 4 + min(int(self.words[i][0]), self.cap)
+                w = self.words[i][:used].copy()
+                if int(self.meta[i][0]) != seq:  # rewritten under the copy: keep the previous one
+                    continue
+                best = (seq, fid, ts, w)
+            if best is not None:
+                self._delivered[s] = best[0]
+                out.append((self.first + s, best[1], best[2], best[3]))
+        return out
+
+    def close(self) -> None:
+        self.hdr = None
+        self.meta = self.ts = self.words = []
+        try:
+            self.shm.close()
+        except Exception:  # pragma: no cover - views still exported
+            pass
+        if self.owner:
+            try:
+                self.shm.unlink()
+            except FileNotFoundError:
+                pass
+
+
+class _RingHub:
+    """The worker's stand-in for the ResultHub: pushes go to the shared-memory ring (and
+    the latest masks to the incarnation's mask channel)."""
+
+    def __init__(self, ring: _RecordRing, masks: Optional[_MaskChannel] = None):
         self.ring = ring
+        self.masks = masks
         self.buffers = {}
         self.depth = 0
 
-    def push_records(self, recs) -> None:
+    def push_records(self, recs, stream: Optional[int] = None) -> None:
         if len(recs):
             self.ring.push(np.ascontiguousarray(recs))
+
+    def push_masks(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """As ResultHub.push_masks: per stream of the batch, its last frame's used words."""
+        if self.masks is None:
+            return
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint32:
+            rows = rows.view(np.uint32)
+        last = {}
+        for i in range(len(rows)):
+            last[int(meta[i, 1])] = i
+        for st, i in last.items():
+            used = 4 + min(int(rows[i, 0]), rows.shape[1] - 4)
+            self.masks.write(st, int(meta[i, 0]), float(meta[i, 2]), rows[i, :used])
 
 
 def _fault_for(spec: Optional[str], rank: int, incarnation: int):
@@ -193,7 +309,7 @@ def _fault_for(spec: Optional[str], rank: int, incarnation: int):
 
 
 def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnation: int,
-                 max_steps: Optional[int]) -> None:
+                 max_steps: Optional[int], mask_name: Optional[str] = None) -> None:
     """Child process: rank ``rank``'s producer, reporting through the ring and ``q``."""
     logging.basicConfig(level=getattr(logging, cfg.log_level.upper(), logging.INFO),
                         format=f"%(asctime)s %(levelname)s worker{rank}: %(message)s")
@@ -206,6 +322,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     from .pipeline import Producer
     from .sources import make_source
     ring = _RecordRing(name=ring_name)
+    masks = _MaskChannel(name=mask_name) if mask_name else None
     metrics = Metrics()
     device = None
     if cfg.device != "cpu" and torch.cuda.is_available() and torch.cuda.device_count() > rank:
@@ -215,7 +332,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     sources = [make_source(cfg.source, rank * S + s, cfg.camera_idx, cfg.camera_width, cfg.camera_height,
                            cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank)
                for s in range(S)]
-    prod = Producer(engine, sources, _RingHub(ring), metrics, cfg.batch, max_steps=max_steps)
+    prod = Producer(engine, sources, _RingHub(ring, masks), metrics, cfg.batch, max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
 
     def on_step(n: int) -> None:  # step progress, published by the producer thread itself
@@ -264,6 +381,7 @@ class _Worker:
         self.incarnation = -1
         self.proc = None
         self.ring: Optional[_RecordRing] = None
+        self.masks: Optional[_MaskChannel] = None
         self.q = None
         self.up = False
         self.started = 0.0
@@ -309,7 +427,9 @@ class SupervisedServer:
         streams = [dict(stream_id=r * self.S + s, width=self.camera_res[0], height=self.camera_res[1],
                         rank=r, source=cfg.source) for r in range(self.nw) for s in range(self.S)]
         S.add_v2_servicer(S.SemanticSegmentationV2Servicer(self.hub, labels, cfg.num_detections,
-                                                           streams, self.metrics, self._health),
+                                                           streams, self.metrics, self._health,
+                                                           serve_masks=cfg.serve_masks,
+                                                           model_size=(cfg.input_size, cfg.input_size)),
                           self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
         self._ctx = mp.get_context("spawn")
@@ -350,9 +470,12 @@ class SupervisedServer:
         w.up = False
         w.q = self._ctx.Queue()
         w.ring = _RecordRing(self.ring_rows)
+        w.masks = _MaskChannel(self.S, int(self.cfg.mask_max_runs), w.rank * self.S) \
+            if self.cfg.serve_masks else None
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
-                                         self.max_steps), daemon=True)
+                                         self.max_steps, w.masks.name if w.masks is not None else None),
+                                   daemon=True)
         w.proc.start()
         w.started = time.time()
         w.progress_seen = w.started
@@ -383,6 +506,9 @@ class SupervisedServer:
         if len(recs):
             self.hub.push_records(recs)
             self.metrics.inc("objects", len(recs))
+        if w.masks is not None:
+            for stream, fid, ts, words in w.masks.pull():
+                self.hub.put_mask(stream, fid, ts, words)
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
@@ -456,6 +582,9 @@ class SupervisedServer:
                 self.metrics.inc("ipc_drops", dropped)
             w.ring.close()
             w.ring = None
+        if w.masks is not None:
+            w.masks.close()
+            w.masks = None
         if w.q is not None:
             try:
                 w.q.close()

@@ -59,7 +59,9 @@ class Server:
         streams = [dict(stream_id=s.stream, width=s.resolution[0], height=s.resolution[1],
                         rank=0, source=cfg.source) for s in self.sources]
         self.v2 = S.SemanticSegmentationV2Servicer(self.hub, self.labels, cfg.num_detections,
-                                                   streams, self.metrics, self._health)
+                                                   streams, self.metrics, self._health,
+                                                   serve_masks=cfg.serve_masks,
+                                                   model_size=(cfg.input_size, cfg.input_size))
         S.add_v1_servicer(self.v1, self.grpc_server)
         S.add_v2_servicer(self.v2, self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
