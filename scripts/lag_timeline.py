@@ -39,7 +39,7 @@ orig = eng.run_device
 
 def run_device(frames):
     i = eng._slot_of.get(frames.data_ptr())
-    st = eng.slot_streams[i] if getattr(eng, "slot_parallel", False) and i is not None else \
+    st = eng.slot_streams[i] if eng.slot_parallel and i is not None else \
         torch.cuda.current_stream()
     e0 = torch.cuda.Event(enable_timing=True)
     e0.record(st)

@@ -313,7 +313,7 @@ class DataParallelPipeline:
             if gather == "rccl":
                 self._gcomm = rccl.StreamComm(ctx, "gather")
         if self.cuda and hasattr(engine, "bind_inputs"):
-            if getattr(engine, "slot_parallel", False):
+            if engine.slot_parallel:
                 self._prime(int(os.environ.get("SSA_PIPE_PRIME", str(8 * self.nslots))))
 
     def rccl_nranks(self) -> Optional[int]:
@@ -467,7 +467,7 @@ class DataParallelPipeline:
         frames = self._frames_for_step()
         labels, packed = self.engine.run_device(frames)
         if self.cuda:
-            consumed = getattr(self.engine, "last_consumed", None)
+            consumed = self.engine.last_consumed
             if consumed is None:  # the model ran on the caller's stream
                 consumed = torch.cuda.Event()
                 consumed.record(torch.cuda.current_stream(self.dev))
@@ -486,7 +486,7 @@ class DataParallelPipeline:
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
         # post-processing runs on a stream of its own: gather + D2H go there too
-        rs = getattr(self.engine, "result_stream", None) if self.cuda else None
+        rs = self.engine.result_stream if self.cuda else None
         if self.gather_mode == "host":
             ev = None
             if rs is not None:

@@ -1,0 +1,160 @@
+"""Captured steps of the engine, one class per capture form: the hipGraphs of one frame buffer
+and the static outputs they write (``labels``; ``post``: packed records or None; ``mask``:
+--serve_masks run words or None). ``replay()`` issues that form's replays, waits and event
+records; after ``consumed`` the buffer may be refilled (None: the model ran on the caller's stream).
+"""
+from __future__ import annotations
+
+import torch
+
+from ..utils import fast_cuda
+
+
+def capture(eng, frames: torch.Tensor, slot: int = None):
+    """The step that runs ``eng`` on ``frames``; ``slot``: the index of a buffer declared
+    with ``bind_inputs`` (None: the engine's static input, always one whole graph)."""
+    dev = eng.device
+    s = torch.cuda.Stream(dev)
+    s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(s):
+        for _ in range(2):  # warm up allocator / lazy init outside capture
+            eng._step_outputs(frames)
+    torch.cuda.current_stream(dev).wait_stream(s)
+    if slot is None or not eng._split:
+        return WholeStep(eng, frames)
+    if eng.slot_parallel:
+        return SlotStep(eng, frames, slot)
+    B, P = frames.shape[0], eng.model_parts if eng._hip_model is not None else 1
+    if P > 1 and B % P == 0 and B >= 2 * P:
+        return PartsStep(eng, frames, P)
+    return SplitStep(eng, frames)
+
+
+def _graph(fn):
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = fn()
+    return g, out
+
+
+class WholeStep:
+    """One graph, model + post-processing (+ masks), on the caller's stream."""
+
+    def __init__(self, eng, frames):
+        self.frames, self.consumed = frames, None
+        self.graph, (self.labels, self.post, self.mask) = _graph(lambda: eng._step_outputs(frames))
+
+    def replay(self) -> None:
+        self.graph.replay()
+
+
+class SplitStep:
+    """The model graph on the caller's stream, the post-processing graph (records, then the
+    run-length masks) on the engine's ``result_stream``."""
+
+    def __init__(self, eng, frames, part: int = 0):
+        hm, dev = eng._hip_model, eng.device
+        self.frames, self.consumed, self.device = frames, None, dev
+        # the model writes the step's own label maps
+        self.labels = lab = torch.empty((frames.shape[0], eng.H, eng.W), dtype=torch.uint8, device=dev)
+        if eng.slot_parallel:  # SlotStep: this slot's plan copy is built outside capture
+            hm.segment(frames, eng.lut_x, eng.lut_y, out=lab, part=part)
+            torch.cuda.synchronize(dev)
+        if hm is not None:
+            self.model, _ = _graph(lambda: hm.segment(frames, eng.lut_x, eng.lut_y, out=lab, part=part))
+        else:
+            self.model, _ = _graph(lambda: lab.copy_(eng._infer_eager(frames)))
+        self.post_graph, (self.post, self.mask) = _graph(lambda: eng._post_and_mask(lab))
+        self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
+
+    def replay(self) -> None:
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(self.post_done)  # this step's previous post-processing read `labels`
+        self.model.replay()
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        rs = self.rs
+        rs.wait_event(ready)
+        with torch.cuda.stream(rs):
+            self.post_graph.replay()
+        self.post_done.record(rs)
+
+
+class SlotStep(SplitStep):
+    """Slot-parallel: the model graph on the staging slot's own stream, with its own plan copy."""
+    # the previous step (other slot, other stream, other plan copy) may still be running.
+    # Per-step host work kept to C calls (utils/fast_cuda.py; the slot's events are reused:
+    # a slot's next step is at least one step later)
+
+    def __init__(self, eng, frames, slot: int):
+        super().__init__(eng, frames, part=slot)
+        self.ms, self.h2d_on_slot, self.device_index = eng.slot_streams[slot], eng.h2d_on_slot, eng.device_index
+        self.fork, self.ready = torch.cuda.Event(), torch.cuda.Event()
+        self.consumed = self.ready  # the staging slot may be refilled after this
+
+    def replay(self) -> None:
+        ms, rs, post_done, ready = self.ms, self.rs, self.post_done, self.ready
+        if self.h2d_on_slot:  # frames were uploaded on ms itself
+            ms.wait_event(post_done)
+        else:
+            cur = fast_cuda.current_stream(self.device_index)
+            cur.wait_event(post_done)  # this slot's previous post-processing read `labels`
+            self.fork.record(cur)  # cur waited for this slot's frames (H2D)
+            ms.wait_event(self.fork)
+        with fast_cuda.StreamSwitch(ms):
+            self.model.replay()
+        ready.record(ms)
+        rs.wait_event(ready)
+        with fast_cuda.StreamSwitch(rs):
+            self.post_graph.replay()
+        post_done.record(rs)
+
+
+class PartsStep:
+    """P sub-batch model graphs on P streams (the caller's and the engine's ``model_streams``),
+    each part's post-processing graph on ``result_stream`` as soon as its labels exist."""
+    # the latency-bound kernels of one part fill the others' tails
+
+    def __init__(self, eng, frames, P: int):
+        hm, dev, B = eng._hip_model, eng.device, frames.shape[0]
+        self.frames, self.consumed, self.device = frames, None, dev
+        sls = [slice(i * (B // P), (i + 1) * (B // P)) for i in range(P)]
+        self.labels = lab = torch.empty((B, eng.H, eng.W), dtype=torch.uint8, device=dev)
+        self.post = post = torch.zeros((B, 1 + 5 * eng.cfg.max_segments), dtype=torch.float32, device=dev)
+        self.mask = mask = torch.zeros((B, 4 + eng.mask_cap), dtype=torch.int32,
+                                       device=dev) if eng.mask_cap else None
+        parts = [(lambda i=i, sl=sl: hm.segment(frames[sl], eng.lut_x, eng.lut_y, out=lab[sl], part=i),
+                  lambda sl=sl: eng._device_post(lab[sl], out=post[sl],
+                                                 mask_out=mask[sl] if mask is not None else None))
+                 for i, sl in enumerate(sls)]  # per part: (model, records)
+        for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
+            run()
+        torch.cuda.synchronize(dev)
+        graphs = [(_graph(m)[0], _graph(r)[0]) for m, r in parts]  # captured in that order
+        self.models, self.posts = zip(*graphs)
+        while len(eng.model_streams) < P - 1:
+            eng.model_streams.append(torch.cuda.Stream(dev))
+        self.side, self.rs, self.post_done = eng.model_streams[:P - 1], eng.result_stream, torch.cuda.Event()
+
+    def replay(self) -> None:
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(self.post_done)  # this step's previous post-processing read `labels`
+        rs = self.rs
+        fork = torch.cuda.Event()
+        fork.record(cur)
+        ready = []
+        for st, g in zip([cur] + self.side, self.models):
+            if st is not cur:
+                st.wait_event(fork)
+            with torch.cuda.stream(st):
+                g.replay()
+            ev = torch.cuda.Event()
+            ev.record(st)
+            ready.append(ev)
+        for ev in ready[1:]:  # cur joins every part: the staging slot is free only after
+            cur.wait_event(ev)  # all of them read it
+        with torch.cuda.stream(rs):
+            for ev, gp in zip(ready, self.posts):
+                rs.wait_event(ev)
+                gp.replay()
+        self.post_done.record(rs)

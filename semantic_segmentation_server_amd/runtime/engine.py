@@ -36,9 +36,8 @@ from ..labels import colormap_for, load_labels
 from ..models.deeplab import build_model
 from ..ops import reference_ops as R
 from ..postprocess import reference as PR
+from .capture import capture
 from .results import RECORD_DTYPE
-
-from ..utils import fast_cuda
 
 log = logging.getLogger(__name__)
 
@@ -100,8 +99,17 @@ class Engine:
             raise RuntimeError("hip backend requires a GPU device")
         self.dtype = DTYPES[cfg.dtype] if self.is_cuda else torch.float32
         self.cam: Optional[Tuple[int, int]] = None
-        self._graph = None
-        self._static: Dict[str, torch.Tensor] = {}
+        # captured steps (runtime/capture.py): the static input's, and one per buffer declared
+        # with bind_inputs, which also decides everything below (defaults: nothing bound)
+        self._static_step = None
+        self._bound, self._slot_of, self._bound_graphs = {}, {}, {}  # keyed by data_ptr()
+        self._split = self.slot_parallel = self.h2d_on_slot = False
+        self.result_stream = self.last_consumed = None
+        self.slot_streams: List[torch.cuda.Stream] = []
+        self.model_streams: List[torch.cuda.Stream] = []
+        self.model_parts = 1
+        self.device_index = (self.device.index if self.device.index is not None
+                             else torch.cuda.current_device() if self.is_cuda else -1)
         self._hip_model = None
         self._hip_post = None
         # --serve_masks: run slots per frame of the label-mask encoder (0 = off: no kernel,
@@ -159,9 +167,8 @@ class Engine:
         self.crop_w, self.crop_h = cw, ch
         self.lut_x = torch.tensor(lx, device=self.device, dtype=torch.int32)
         self.lut_y = torch.tensor(ly, device=self.device, dtype=torch.int32)
-        self._graph = None
-        if getattr(self, "_bound_graphs", None):
-            self._bound_graphs = {}  # captured for the previous camera's letterbox
+        self._static_step = None  # captured for the previous camera's letterbox,
+        self._bound_graphs = {}  # like the bound buffers' steps
 
     # -------------------------------------------------------------- inference
     def _infer_eager(self, frames: torch.Tensor) -> torch.Tensor:
@@ -174,9 +181,13 @@ class Engine:
         return R.upsample_argmax(logits, self.H, self.W)
 
     def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
-                     mask_out: Optional[torch.Tensor] = None):
-        """Device records of ``labels`` and, with ``mask_cap``, their run-length masks
-        right after on the same stream (``mask_packed``): one captured graph holds both."""
+                     mask_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._post_and_mask(labels, out, mask_out)[0]  # the records alone
+
+    def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       mask_out: Optional[torch.Tensor] = None):
+        """(device records of ``labels``, with ``mask_cap`` their run-length masks else None),
+        the masks right after the records on the same stream: one captured graph holds both."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -187,9 +198,7 @@ class Engine:
                                                mask_cap=self.mask_cap)
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
                                  mask_out=mask_out)
-        if self.mask_cap:
-            self.mask_packed = self._hip_post.last_mask
-        return rec
+        return rec, (self._hip_post.last_mask if self.mask_cap else None)
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
@@ -204,18 +213,21 @@ class Engine:
             MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
         return out
 
-    def _step_device(self, frames: torch.Tensor):
+    def _step_outputs(self, frames: torch.Tensor):
+        """One eager step: (labels, packed records or None, mask run words or None)."""
         labels = self._infer_eager(frames)
         if self._use_device_post():
-            return labels, self._device_post(labels)
-        if self.mask_cap:
-            # no device post-processing: on the CPU the masks are encoded here; a GPU's host
-            # post-processing path encodes them where it brings the label maps to the host
-            self.mask_packed = None if self.is_cuda else \
-                torch.from_numpy(self.host_masks(labels).view(np.int32))
-        if not self.is_cuda and self.cfg.contour_mode != "none":
-            return labels, self._host_packed(labels)
-        return labels, None
+            return (labels, *self._post_and_mask(labels))
+        # no device post-processing: on the CPU the masks are encoded here; a GPU's host
+        # post-processing path encodes them where it brings the label maps to the host
+        host = not self.is_cuda
+        mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
+        post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
+        return labels, post, mask
+
+    def _step_device(self, frames: torch.Tensor):
+        labels, post, self.mask_packed = self._step_outputs(frames)
+        return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
         """CPU path: host post-processing packed like the device output
@@ -233,24 +245,10 @@ class Engine:
                 out[b, 1:1 + 5 * len(r)] = torch.from_numpy(vals.reshape(-1))
         return out
 
-    def _capture(self, B: int) -> None:
-        Hc, Wc = self.cam[1], self.cam[0]
-        st = self._static
-        st["frames"] = torch.zeros((B, Hc, Wc, 3), dtype=torch.uint8, device=self.device)
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            for _ in range(2):  # warm up allocator / lazy init outside capture
-                self._step_device(st["frames"])
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            labels, post = self._step_device(st["frames"])
-        st["labels"] = labels
-        st["post"] = post
-        st["mask"] = self.mask_packed
-        self._graph = g
-        self._graph_B = B
+    @property
+    def _static(self) -> Dict[str, torch.Tensor]:
+        """The static step's frames, labels, post, mask (empty before the first static run)."""
+        return vars(self._static_step) if self._static_step is not None else {}
 
     def bind_inputs(self, bufs, split_post: bool = False) -> None:
         """Declare persistent frame buffers (e.g. the DP pipeline's double-buffered
@@ -277,7 +275,7 @@ class Engine:
         # 24.0k for one graph (profiles/r2_parts_ab.txt); slot-parallel (default, below)
         # measured faster still, so parts are off unless asked for.
         self.model_parts = int(os.environ.get("SSA_MODEL_PARTS", "1"))
-        self.model_streams: List[torch.cuda.Stream] = []
+        self.model_streams = []
         self._bound = {b.data_ptr(): b for b in bufs}
         self._slot_of = {b.data_ptr(): i for i, b in enumerate(bufs)}
         # slot-parallel (default; SSA_SLOT_PARALLEL=0 turns it off): every staging slot owns
@@ -292,10 +290,6 @@ class Engine:
         # has no plan, so its slots stay on the caller's stream)
         self.slot_parallel = (os.environ.get("SSA_SLOT_PARALLEL", "1") == "1" and self._split
                               and self._hip_model is not None)
-        self.slot_streams: List[torch.cuda.Stream] = []
-        self._slot_ev: List[tuple] = []  # per slot: (fork, ready) events, reused every step
-        self.device_index = (self.device.index if self.device.index is not None
-                             else torch.cuda.current_device() if self.is_cuda else -1)
         self.last_consumed = None
         # uploads on the slot streams (default; SSA_H2D_ON_SLOT=0: a copy stream): the
         # pipeline uploads a slot's frames on that slot's model stream, in order before its
@@ -303,86 +297,22 @@ class Engine:
         # (2 slots + result) on the 4 hardware queues. B = 32 28.0k / 28.1k vs 27.5k / 26.9k
         # frames/s; batch 1 0.340 / 0.356 vs 0.381 / 0.379 ms (profiles/r2_h2d_ab.txt)
         self.h2d_on_slot = self.slot_parallel and os.environ.get("SSA_H2D_ON_SLOT", "1") == "1"
-        if self.slot_parallel:
-            self.slot_streams = [torch.cuda.Stream(self.device) for _ in bufs]
+        self.slot_streams = [torch.cuda.Stream(self.device) for _ in bufs] if self.slot_parallel else []
         self._bound_graphs = {}
         if self.cam is not None:  # capture now, not inside the first timed steps
             for b in bufs:
-                self._bound_graph(b)
+                self._bound_step(b)
 
-    def _bound_graph(self, frames: torch.Tensor):
-        bound = getattr(self, "_bound", None)
-        if not bound:
-            return None
+    def _bound_step(self, frames: torch.Tensor):
+        """The captured step of a buffer declared with ``bind_inputs`` (None: not one)."""
         key = frames.data_ptr()
-        b = bound.get(key)
+        b = self._bound.get(key)
         if b is None or b.shape != frames.shape or b.dtype != frames.dtype:
             return None
-        ent = self._bound_graphs.get(key)
-        if ent is None or ent[0] != tuple(frames.shape):
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                for _ in range(2):  # warm up allocator / lazy init outside capture
-                    self._step_device(b)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            if getattr(self, "_split", False):
-                lab = torch.empty((b.shape[0], self.H, self.W), dtype=torch.uint8, device=self.device)
-                hm = self._hip_model
-                B = b.shape[0]
-                P = self.model_parts if hm is not None and not self.slot_parallel else 1
-                P = P if P > 1 and B % P == 0 and B >= 2 * P else 1
-                if P > 1:
-                    # P independent sub-batch model graphs, replayed on P streams: the
-                    # latency-bound kernels of one part fill the others' tails; each
-                    # part's post-processing starts as soon as its labels exist
-                    h = B // P
-                    sls = [slice(i * h, (i + 1) * h) for i in range(P)]
-                    for part, sl in enumerate(sls):
-                        hm.segment(b[sl], self.lut_x, self.lut_y, out=lab[sl], part=part)
-                    post = torch.zeros((B, 1 + 5 * self.cfg.max_segments), dtype=torch.float32,
-                                       device=self.device)
-                    mask = torch.zeros((B, 4 + self.mask_cap), dtype=torch.int32,
-                                       device=self.device) if self.mask_cap else None
-                    msl = [mask[sl] if mask is not None else None for sl in sls]
-                    for sl, m_ in zip(sls, msl):  # warm-up outside capture
-                        self._device_post(lab[sl], out=post[sl], mask_out=m_)
-                    torch.cuda.synchronize(self.device)
-                    gm, gp = [], []
-                    for part, sl in enumerate(sls):
-                        g_ = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g_):
-                            hm.segment(b[sl], self.lut_x, self.lut_y, out=lab[sl], part=part)
-                        gm.append(g_)
-                        g_ = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g_):
-                            self._device_post(lab[sl], out=post[sl], mask_out=msl[part])
-                        gp.append(g_)
-                    while len(self.model_streams) < P - 1:
-                        self.model_streams.append(torch.cuda.Stream(self.device))
-                else:
-                    if hm is not None and self.slot_parallel:
-                        hm.segment(b, self.lut_x, self.lut_y, out=lab, part=self._slot_of[key])
-                        torch.cuda.synchronize(self.device)
-                    gm = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gm):  # the model writes the slot's own label maps
-                        if hm is not None:
-                            hm.segment(b, self.lut_x, self.lut_y, out=lab,
-                                       part=self._slot_of[key] if self.slot_parallel else 0)
-                        else:
-                            lab.copy_(self._infer_eager(b))
-                    gp = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gp):  # records, then (serve_masks) the run-length masks
-                        post = self._device_post(lab)
-                    mask = self.mask_packed
-                ent = (tuple(frames.shape), gm, lab, post, gp, torch.cuda.Event(), mask)
-            else:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    labels, post = self._step_device(b)
-                ent = (tuple(frames.shape), g, labels, post, None, None, self.mask_packed)
-            self._bound_graphs[key] = ent
-        return ent
+        step = self._bound_graphs.get(key)
+        if step is None:
+            step = self._bound_graphs[key] = capture(self, b, slot=self._slot_of[key])
+        return step
 
     def preferred_lag(self) -> int:
         """Pipeline lag this engine runs best at: 2 (three staging slots, three steps in
@@ -399,7 +329,7 @@ class Engine:
 
     def upload_stream(self, buf: torch.Tensor):
         """Stream to upload a bound staging slot's frames on (SSA_H2D_ON_SLOT), else None."""
-        if not getattr(self, "h2d_on_slot", False):
+        if not self.h2d_on_slot:
             return None
         i = self._slot_of.get(buf.data_ptr())
         return None if i is None else self.slot_streams[i]
@@ -412,89 +342,19 @@ class Engine:
         Frames in a buffer declared with ``bind_inputs`` run that buffer's own graph
         (with ``split_post``, the records are produced on ``result_stream``).
         """
-        B = frames.shape[0]
-        if self.cfg.graph and self.is_cuda:
-            ent = self._bound_graph(frames)
-            if ent is not None:
-                _, g, labels, post, gpost, post_done, mask = ent
-                if mask is not None:  # written by the replay below, like `post`
-                    self.mask_packed = mask
-                if gpost is None:
-                    g.replay()
-                    return labels, post
-                if self.slot_parallel:
-                    # this slot's model on its own stream: the previous step (other slot,
-                    # other stream, other plan copy) may still be running. Per-step host work
-                    # kept to C calls (utils/fast_cuda.py; per-slot events reused: a slot's
-                    # next step is at least one step later)
-                    i = self._slot_of[frames.data_ptr()]
-                    while len(self.slot_streams) <= i:
-                        self.slot_streams.append(torch.cuda.Stream(self.device))
-                    while len(self._slot_ev) <= i:
-                        self._slot_ev.append((torch.cuda.Event(), torch.cuda.Event()))
-                    fork, ready = self._slot_ev[i]
-                    ms, rs = self.slot_streams[i], self.result_stream
-                    if self.h2d_on_slot:  # frames were uploaded on ms itself
-                        ms.wait_event(post_done)
-                    else:
-                        cur = fast_cuda.current_stream(self.device_index)
-                        cur.wait_event(post_done)  # this slot's previous post-processing read `labels`
-                        fork.record(cur)  # cur waited for this slot's frames (H2D)
-                        ms.wait_event(fork)
-                    with fast_cuda.StreamSwitch(ms):
-                        g.replay()
-                    ready.record(ms)
-                    self.last_consumed = ready  # the staging slot may be refilled after this
-                    rs.wait_event(ready)
-                    with fast_cuda.StreamSwitch(rs):
-                        gpost.replay()
-                    post_done.record(rs)
-                    return labels, post
-                cur = torch.cuda.current_stream(self.device)
-                if not self.h2d_on_slot:
-                    cur.wait_event(post_done)  # this slot's previous post-processing read `labels`
-                if isinstance(g, list):
-                    # model parts on cur + model_streams, each part's post-processing on
-                    # the result stream as soon as its labels exist; cur joins every part
-                    # (the staging slot is free only after all of them read it)
-                    rs = self.result_stream
-                    streams = [cur] + self.model_streams[:len(g) - 1]
-                    fork = torch.cuda.Event()
-                    fork.record(cur)
-                    ready = []
-                    for st_, g_ in zip(streams, g):
-                        if st_ is not cur:
-                            st_.wait_event(fork)
-                        with torch.cuda.stream(st_):
-                            g_.replay()
-                        ev = torch.cuda.Event()
-                        ev.record(st_)
-                        ready.append(ev)
-                    for ev in ready[1:]:
-                        cur.wait_event(ev)
-                    with torch.cuda.stream(rs):
-                        for ev, gp_ in zip(ready, gpost):
-                            rs.wait_event(ev)
-                            gp_.replay()
-                    post_done.record(rs)
-                    return labels, post
-                g.replay()
-                ready = torch.cuda.Event()
-                ready.record(cur)
-                rs = self.result_stream
-                rs.wait_event(ready)
-                with torch.cuda.stream(rs):
-                    gpost.replay()
-                post_done.record(rs)
-                return labels, post
-            if self._graph is None or self._graph_B != B:
-                self._capture(B)
-            self._static["frames"].copy_(frames, non_blocking=True)
-            self._graph.replay()
-            if self.mask_cap:
-                self.mask_packed = self._static["mask"]
-            return self._static["labels"], self._static["post"]
-        return self._step_device(frames)
+        if not (self.cfg.graph and self.is_cuda):
+            return self._step_device(frames)
+        step = self._bound_step(frames)
+        if step is None:  # the engine's own static input buffer, for this batch size
+            step, B = self._static_step, frames.shape[0]
+            if step is None or step.frames.shape[0] != B:
+                buf = torch.zeros((B, self.cam[1], self.cam[0], 3), dtype=torch.uint8, device=self.device)
+                step = self._static_step = capture(self, buf)
+            step.frames.copy_(frames, non_blocking=True)
+        step.replay()
+        # written by the replay, like the records; and when the frame buffer may be refilled
+        self.mask_packed, self.last_consumed = step.mask, step.consumed
+        return step.labels, step.post
 
     # ------------------------------------------------------------ post/host
     def records_from_labels(self, labels: torch.Tensor, frame_ids: Sequence[int],

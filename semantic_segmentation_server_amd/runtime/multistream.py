@@ -37,6 +37,11 @@ class StreamGroup:
         self.streams = [e.stream for e in self.engines]
         self.backend = self.engines[0].backend
         self._out = {}
+        # what the pipeline reads of an engine; bind_inputs decides the first two
+        self._split = False
+        self.result_stream = None
+        self.slot_parallel = False  # the streams' models run on their engines' streams and
+        self.last_consumed = None   # are joined on the caller's, which is what read the frames
 
     @property
     def H(self):
@@ -66,7 +71,7 @@ class StreamGroup:
         split_post = bool(split_post) and 2 * S + 1 <= int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
         for i, e in enumerate(self.engines):
             e.bind_inputs([b.chunk(S)[i] for b in bufs], split_post=split_post)
-        self._split = bool(split_post) and all(getattr(e, "_split", False) for e in self.engines)
+        self._split = bool(split_post) and all(e._split for e in self.engines)
         self.result_stream = torch.cuda.Stream(self.device) if self._split else None
         self._copied = [torch.cuda.Event() for _ in self.engines] if self._split else None
 
@@ -87,8 +92,7 @@ class StreamGroup:
             return None, out
         cur = torch.cuda.current_stream(self.device)
         n = B // S
-        split = getattr(self, "_split", False)
-        rs = self.result_stream if split else None
+        split, rs = self._split, self.result_stream
         for i, (e, st, c) in enumerate(zip(self.engines, self.streams, chunks)):
             st.wait_stream(cur)
             with torch.cuda.stream(st):

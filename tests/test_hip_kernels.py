@@ -852,6 +852,29 @@ def test_engine_bound_input_graphs(split):
         assert torch.equal(got, want) and _records_equal(post, eng._device_post(want))
     assert len(eng._bound_graphs) == 2
 
+    def check(frames):
+        f, _, _ = src.read_batch(2)
+        frames.copy_(torch.from_numpy(f))
+        torch.cuda.synchronize()
+        want = eng._infer_eager(frames).clone()
+        want_post = eng._device_post(want).clone()
+        torch.cuda.synchronize()
+        got, post = eng.run_device(frames)
+        torch.cuda.synchronize()
+        assert torch.equal(got, want) and _records_equal(post, want_post)
+
+    # an unbound tensor of the same shape takes the static input's step beside the bound ones
+    check(torch.empty_like(bufs[0]))
+    assert len(eng._bound_graphs) == 2
+    # a camera change drops the bound steps: new buffers run the new letterbox, the old are gone
+    eng.set_camera(160, 120)
+    src = SyntheticSource(160, 120, pool=4, seed=3)
+    bufs = [torch.empty((2, 120, 160, 3), dtype=torch.uint8, device=DEV) for _ in range(2)]
+    eng.bind_inputs(bufs, split_post=split)
+    for b in bufs:
+        check(b)
+    assert len(eng._bound_graphs) == 2
+
 
 @pytest.mark.parametrize("ingest", ["local", "scatter"])
 def test_rccl_world1_pipeline_records_match_eager(ingest):
