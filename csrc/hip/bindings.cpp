@@ -432,6 +432,12 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.attr("MASK_RLE_CHUNK") = mask_rle_chunk();
 
+  m.def("yuv422_to_bgr",
+        [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
+          yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));
+        },
+        py::arg("src"), py::arg("dst"), py::arg("n_macropixels"), py::arg("uyvy"), py::arg("stream"));
+
   m.attr("ACT_NONE") = (int)ACT_NONE;
   m.attr("ACT_RELU") = (int)ACT_RELU;
   m.attr("ACT_RELU6") = (int)ACT_RELU6;

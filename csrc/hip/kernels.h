@@ -328,4 +328,10 @@ void mask_rle(const MaskRleParams& p, hipStream_t s);
 // only the 4 + min(n_runs, cap) used words are written, by a kernel on stream s.
 void mask_rle_copy_used(const uint32_t* src, uint32_t* dst, int B, int cap, hipStream_t s);
 
+// ---- raw 4:2:2 ingest (yuv422.hip) -------------------------------------------
+// n_macropixels packed macropixels (4 bytes each; YUYV: Y0 U Y1 V, uyvy: U Y0 V Y1) -> BGR
+// (6 bytes each), bit-identical to the host conversion (csrc/host/v4l2.cpp). src: any
+// 4-byte-aligned address, dst: any 2-byte-aligned one, n_macropixels >= 1.
+void yuv422_to_bgr(const uint8_t* src, uint8_t* dst, size_t n_macropixels, bool uyvy, hipStream_t s);
+
 }  // namespace ssa

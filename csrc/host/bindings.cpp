@@ -143,15 +143,29 @@ PYBIND11_MODULE(_host, m) {
   }, py::arg("src"), py::arg("uyvy") = false,
         "Packed 4:2:2 (YUYV, or UYVY) -> BGR, BT.601 limited range (OpenCV's COLOR_YUV2BGR_YUYV convention).");
 
+  m.def("copy_packed_rows", [](const U8& src, int pitch, int W, int H) {
+    // src: a flat driver buffer of at least pitch * (H - 1) + 2 * W bytes
+    if (W < 0 || H < 0 || pitch < 2 * W) throw std::invalid_argument("copy_packed_rows: pitch < 2 * W");
+    const size_t need = H ? (size_t)pitch * (H - 1) + (size_t)2 * W : 0;
+    if ((size_t)src.size() < need) throw std::invalid_argument("copy_packed_rows: src is shorter than the frame");
+    py::array_t<uint8_t> out({(ssize_t)H, (ssize_t)W, (ssize_t)2});
+    copy_packed_rows(src.data(), pitch, 2 * W, H, out.mutable_data());
+    return out;
+  }, py::arg("src"), py::arg("pitch"), py::arg("W"), py::arg("H"),
+        "Packed 4:2:2 rows `pitch` bytes apart -> a dense (H, W, 2) frame (the raw-mode capture copy).");
+
   py::class_<V4L2Capture>(m, "V4L2Capture")
-      .def(py::init<const std::string&, int, int, int>(), py::arg("device"), py::arg("width") = 640,
-           py::arg("height") = 480, py::arg("nbuf") = 4)
+      .def(py::init<const std::string&, int, int, int, const std::string&>(), py::arg("device"),
+           py::arg("width") = 640, py::arg("height") = 480, py::arg("nbuf") = 4, py::arg("raw_format") = "")
       .def_property_readonly("width", &V4L2Capture::width)
       .def_property_readonly("height", &V4L2Capture::height)
       .def_property_readonly("fourcc", &V4L2Capture::fourcc)
+      .def_property_readonly("raw", &V4L2Capture::raw)
       .def("read_into", [](V4L2Capture& c, py::array_t<uint8_t, py::array::c_style> dst, int timeout_ms) {
-             if (dst.ndim() != 3 || dst.shape(0) != c.height() || dst.shape(1) != c.width() || dst.shape(2) != 3)
-               throw std::invalid_argument("read_into: dst must be (height, width, 3) uint8");
+             if (dst.ndim() != 3 || dst.shape(0) != c.height() || dst.shape(1) != c.width() ||
+                 dst.shape(2) != c.channels())
+               throw std::invalid_argument(c.raw() ? "read_into: dst must be (height, width, 2) uint8 in raw mode"
+                                                   : "read_into: dst must be (height, width, 3) uint8");
              uint32_t seq = 0;
              int64_t ts = 0;
              bool ok;
@@ -161,6 +175,7 @@ PYBIND11_MODULE(_host, m) {
              }
              return py::make_tuple(ok, seq, ts);
            }, py::arg("dst"), py::arg("timeout_ms") = 1000,
-           "Next frame as BGR into dst; returns (ok, driver sequence, timestamp us).")
+           "Next frame as BGR (raw mode: its packed 4:2:2 bytes) into dst; returns (ok, driver "
+           "sequence, timestamp us).")
       .def("close", &V4L2Capture::close);
 }

@@ -60,7 +60,33 @@ void yuv422_to_bgr(const uint8_t* src, int pitch, int W, int H, bool uyvy, uint8
   }
 }
 
-V4L2Capture::V4L2Capture(const std::string& device, int width, int height, int nbuf) {
+void copy_packed_rows(const uint8_t* src, int pitch, int row_bytes, int H, uint8_t* dst) {
+  if (row_bytes < 0 || H < 0 || pitch < row_bytes)
+    throw std::invalid_argument("copy_packed_rows: pitch must be at least the row's bytes");
+  if (pitch == row_bytes) {
+    std::memcpy(dst, src, (size_t)row_bytes * H);
+    return;
+  }
+  for (int y = 0; y < H; ++y) std::memcpy(dst + (size_t)y * row_bytes, src + (size_t)y * pitch, row_bytes);
+}
+
+namespace {
+
+std::string fourcc_str(uint32_t f) {
+  char s[5] = {(char)(f & 255), (char)((f >> 8) & 255), (char)((f >> 16) & 255), (char)(f >> 24), 0};
+  return s;
+}
+
+}  // namespace
+
+V4L2Capture::V4L2Capture(const std::string& device, int width, int height, int nbuf,
+                         const std::string& raw_format) {
+  uint32_t raw_fmt = 0;
+  if (raw_format == "yuyv") raw_fmt = V4L2_PIX_FMT_YUYV;
+  else if (raw_format == "uyvy") raw_fmt = V4L2_PIX_FMT_UYVY;
+  else if (!raw_format.empty())
+    throw std::invalid_argument("v4l2: raw_format must be \"\", \"yuyv\" or \"uyvy\", got \"" + raw_format + "\"");
+  raw_ = raw_fmt != 0;
   fd_ = ::open(device.c_str(), O_RDWR | O_NONBLOCK);
   if (fd_ < 0) fail("open " + device);
   try {
@@ -73,13 +99,27 @@ V4L2Capture::V4L2Capture(const std::string& device, int width, int height, int n
     const uint32_t want[] = {V4L2_PIX_FMT_YUYV, V4L2_PIX_FMT_UYVY, V4L2_PIX_FMT_BGR24, V4L2_PIX_FMT_RGB24};
     bool ok = false;
     for (uint32_t pf : want) {
+      if (raw_ && pf != raw_fmt) continue;  // raw mode: exactly the configured fourcc
       v4l2_format f{};
       f.type = V4L2_BUF_TYPE_VIDEO_CAPTURE;
       f.fmt.pix.width = width;
       f.fmt.pix.height = height;
       f.fmt.pix.pixelformat = pf;
       f.fmt.pix.field = V4L2_FIELD_NONE;
-      if (xioctl(fd_, VIDIOC_S_FMT, &f) == 0 && f.fmt.pix.pixelformat == pf) {
+      const int r = xioctl(fd_, VIDIOC_S_FMT, &f);
+      if (raw_ && (r != 0 || f.fmt.pix.pixelformat != pf)) {
+        // name what the driver would deliver, and the flag that ingests it
+        std::string got = "no format (VIDIOC_S_FMT failed)", flag = "bgr";
+        if (r == 0) {
+          got = fourcc_str(f.fmt.pix.pixelformat);
+          if (f.fmt.pix.pixelformat == V4L2_PIX_FMT_YUYV) flag = "yuyv";
+          if (f.fmt.pix.pixelformat == V4L2_PIX_FMT_UYVY) flag = "uyvy";
+        }
+        throw std::runtime_error("v4l2: " + device + " does not deliver " + fourcc_str(pf) +
+                                 " (--pixel_format " + raw_format + "): the driver negotiated " + got +
+                                 "; use --pixel_format " + flag);
+      }
+      if (r == 0 && f.fmt.pix.pixelformat == pf) {
         fmt_ = pf;
         w_ = (int)f.fmt.pix.width;
         h_ = (int)f.fmt.pix.height;
@@ -119,10 +159,7 @@ V4L2Capture::V4L2Capture(const std::string& device, int width, int height, int n
 
 V4L2Capture::~V4L2Capture() { close(); }
 
-std::string V4L2Capture::fourcc() const {
-  char s[5] = {(char)(fmt_ & 255), (char)((fmt_ >> 8) & 255), (char)((fmt_ >> 16) & 255), (char)(fmt_ >> 24), 0};
-  return s;
-}
+std::string V4L2Capture::fourcc() const { return fourcc_str(fmt_); }
 
 bool V4L2Capture::read(uint8_t* dst, int timeout_ms, uint32_t* seq, int64_t* ts_us) {
   if (fd_ < 0) return false;
@@ -143,7 +180,9 @@ bool V4L2Capture::read(uint8_t* dst, int timeout_ms, uint32_t* seq, int64_t* ts_
   const size_t need = (size_t)pitch_ * (h_ - 1) + (size_t)w_ * (fmt_ == V4L2_PIX_FMT_YUYV || fmt_ == V4L2_PIX_FMT_UYVY ? 2 : 3);
   bool good = b.bytesused == 0 || b.bytesused >= need;  // some drivers leave bytesused 0
   if (good) {
-    if (fmt_ == V4L2_PIX_FMT_YUYV || fmt_ == V4L2_PIX_FMT_UYVY) {
+    if (raw_) {
+      copy_packed_rows(src, pitch_, 2 * w_, h_, dst);
+    } else if (fmt_ == V4L2_PIX_FMT_YUYV || fmt_ == V4L2_PIX_FMT_UYVY) {
       yuv422_to_bgr(src, pitch_, w_, h_, fmt_ == V4L2_PIX_FMT_UYVY, dst);
     } else {
       const bool rgb = fmt_ == V4L2_PIX_FMT_RGB24;

@@ -17,11 +17,20 @@ namespace ssa {
 // YUYV (Y0 U Y1 V) / UYVY (U Y0 V Y1) -> BGR, one row pitch `pitch` bytes.
 void yuv422_to_bgr(const uint8_t* src, int pitch, int W, int H, bool uyvy, uint8_t* dst);
 
+// H rows of `row_bytes` payload bytes each, `pitch` (>= row_bytes) bytes apart in src ->
+// dst, densely packed (the raw-mode frame copy: packed 4:2:2 rows are 2 * W bytes).
+void copy_packed_rows(const uint8_t* src, int pitch, int row_bytes, int H, uint8_t* dst);
+
 class V4L2Capture {
  public:
   // Opens `device`, asks for width x height (the driver may pick another size; see
   // width()/height()), nbuf mmap buffers. Throws std::runtime_error on failure.
-  V4L2Capture(const std::string& device, int width, int height, int nbuf = 4);
+  // raw_format "" (default): negotiate YUYV / UYVY / BGR24 / RGB24 and deliver BGR.
+  // raw_format "yuyv" | "uyvy": request exactly that packed 4:2:2 format and deliver its
+  // bytes unconverted (read() then fills height x width x 2); throws, naming the format the
+  // driver negotiated instead, when it is not granted.
+  V4L2Capture(const std::string& device, int width, int height, int nbuf = 4,
+              const std::string& raw_format = "");
   ~V4L2Capture();
   V4L2Capture(const V4L2Capture&) = delete;
   V4L2Capture& operator=(const V4L2Capture&) = delete;
@@ -29,8 +38,11 @@ class V4L2Capture {
   int width() const { return w_; }
   int height() const { return h_; }
   std::string fourcc() const;
+  bool raw() const { return raw_; }
+  int channels() const { return raw_ ? 2 : 3; }  // bytes per pixel read() delivers
   // Dequeues the next frame (waits at most timeout_ms), converts it to BGR into dst
-  // (height x width x 3) and re-queues the buffer. Returns false on timeout / EOF.
+  // (height x width x 3; raw mode: copies the packed rows into height x width x 2)
+  // and re-queues the buffer. Returns false on timeout / EOF.
   // seq / ts_us: driver sequence number and capture timestamp (microseconds).
   bool read(uint8_t* dst, int timeout_ms, uint32_t* seq, int64_t* ts_us);
   void close();
@@ -43,6 +55,7 @@ class V4L2Capture {
   Buf bufs_[16] = {};
   int nbuf_ = 0;
   bool streaming_ = false;
+  bool raw_ = false;
 };
 
 }  // namespace ssa

@@ -19,6 +19,9 @@ from typing import List, Optional
 from .labels import CITYSCAPES_LABELS, PASCAL_LABELS
 
 
+PIXEL_FORMATS = ("bgr", "yuyv", "uyvy")
+
+
 @dataclass
 class Config:
     # --- reference flags ---
@@ -40,6 +43,7 @@ class Config:
     camera_height: int = 480
     streams: int = 1                       # camera streams per rank
     fps_limit: Optional[float] = None
+    pixel_format: str = "bgr"              # bgr | yuyv | uyvy (raw packed 4:2:2, converted on the device)
     # --- model ---
     arch: str = "mnv2"                     # mnv2 | resnet50
     num_classes: int = 21
@@ -75,6 +79,24 @@ class Config:
     debug_every: int = 0                   # dump every N-th frame (0 = off)
     debug_sync: bool = False               # HIP_LAUNCH_BLOCKING=1, eager launches
     supervise: bool = True                 # CLI: GPU work in supervised worker processes (one per GPU)
+
+    def __post_init__(self):
+        if self.pixel_format not in PIXEL_FORMATS:
+            raise ValueError(f"--pixel_format must be one of {', '.join(PIXEL_FORMATS)}, "
+                             f"got {self.pixel_format!r}")
+        if self.pixel_format != "bgr":
+            if self.camera_width % 2:
+                raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
+                                 f"--camera_width {self.camera_width} must be even")
+            if self.ingest == "scatter":
+                raise ValueError(f"--ingest scatter is not supported with --pixel_format "
+                                 f"{self.pixel_format}: the scatter path moves BGR frames only; "
+                                 "use --ingest local")
+
+    @property
+    def frame_channels(self) -> int:
+        """Bytes per pixel of an ingested frame: 3 (BGR) or 2 (packed 4:2:2)."""
+        return 3 if self.pixel_format == "bgr" else 2
 
     @property
     def min_area(self) -> float:
@@ -113,6 +135,9 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--camera_height", type=int, default=d.camera_height)
     p.add_argument("--streams", type=int, default=d.streams)
     p.add_argument("--fps_limit", type=float, default=d.fps_limit)
+    p.add_argument("--pixel_format", choices=list(PIXEL_FORMATS), default=d.pixel_format,
+                   help="format of the ingested frames: bgr, or raw packed 4:2:2 (yuyv | uyvy) "
+                        "uploaded at 2 bytes per pixel and converted to BGR on the device")
     p.add_argument("--arch", choices=["mnv2", "resnet50"], default=d.arch)
     p.add_argument("--num_classes", type=int, default=d.num_classes)
     p.add_argument("--dataset", choices=["pascal", "cityscapes"], default=d.dataset)

@@ -1161,6 +1161,26 @@ def mask_rle_copy_to_host(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     return dst
 
 
+def yuv422_to_bgr(src: torch.Tensor, out: torch.Tensor, uyvy: bool = False) -> torch.Tensor:
+    """Packed 4:2:2 frames ``src`` (B, H, W, 2) uint8 (YUYV: Y0 U Y1 V; ``uyvy``: U Y0 V Y1)
+    -> BGR ``out`` (B, H, W, 3) uint8 (csrc/hip/yuv422.hip), bit-identical to the host
+    conversion (``ops.native.host().yuv422_to_bgr``). Batch slices of contiguous tensors are
+    fine: the kernel takes any 4-byte-aligned source and 2-byte-aligned destination."""
+    _chk(src, torch.uint8, "src")
+    _chk(out, torch.uint8, "out")
+    if src.dim() != 4 or src.shape[3] != 2 or src.shape[2] % 2 or src.numel() == 0:
+        raise ValueError(f"src: shape {tuple(src.shape)} is not (B, H, W, 2) with even W")
+    if tuple(out.shape) != tuple(src.shape[:3]) + (3,):
+        raise ValueError(f"out: shape {tuple(out.shape)} != {tuple(src.shape[:3]) + (3,)}")
+    if out.device != src.device:
+        raise ValueError("yuv422_to_bgr: src and out are on different devices")
+    if src.data_ptr() % 4 or out.data_ptr() % 2:
+        raise ValueError("yuv422_to_bgr: src must be 4-byte and out 2-byte aligned")
+    _hip_mod().yuv422_to_bgr(_ptr(src), _ptr(out), src.numel() // 4, bool(uyvy), _stream())
+    _dbg('yuv422_to_bgr')
+    return out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

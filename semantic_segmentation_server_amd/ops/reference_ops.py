@@ -70,6 +70,27 @@ def preprocess(frames_bgr: torch.Tensor, lut_x, lut_y, out_dtype=torch.float32,
     return out.to(out_dtype)
 
 
+def yuv422_to_bgr(frames: torch.Tensor, uyvy: bool = False) -> torch.Tensor:
+    """Packed 4:2:2 uint8 frames (..., W, 2), W even (YUYV: Y0 U Y1 V; ``uyvy``: U Y0 V Y1)
+    -> BGR (..., W, 3) uint8 in torch ops, on any device: the int32 arithmetic of the host
+    conversion (csrc/host/v4l2.cpp ``px2``: BT.601 limited range in 20-bit fixed point, an
+    arithmetic shift -- not a truncating division --, saturation to 0..255). The torch and
+    CPU paths of raw ingest, and with the host function the oracle of csrc/hip/yuv422.hip."""
+    if frames.dtype != torch.uint8 or frames.dim() < 2 or frames.shape[-1] != 2 or frames.shape[-2] % 2:
+        raise ValueError(f"yuv422_to_bgr: expected uint8 (..., W, 2) with even W, got "
+                         f"{frames.dtype} {tuple(frames.shape)}")
+    lead, W = tuple(frames.shape[:-2]), frames.shape[-2]
+    mp = frames.reshape(lead + (W // 2, 4)).to(torch.int32)
+    iy0, iu, iy1, iv = (1, 0, 3, 2) if uyvy else (0, 1, 2, 3)
+    du, dv = mp[..., iu] - 128, mp[..., iv] - 128
+    half = 1 << 19
+    uv = torch.stack([half + 2116026 * du, half - 852492 * dv - 409993 * du, half + 1673527 * dv], -1)
+    y = torch.stack([mp[..., iy0], mp[..., iy1]], -1)                  # ..., W/2, 2
+    c = (y - 16).clamp_(min=0) * 1220542
+    bgr = (c[..., :, None] + uv[..., None, :]) >> 20                   # ..., W/2, 2, 3
+    return bgr.clamp_(0, 255).to(torch.uint8).reshape(lead + (W, 3))
+
+
 def upsample_argmax(logits: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """(N, K, h, w) logits -> (N, H, W) uint8 labels: bilinear align_corners=True
     then argmax over K (first max wins, as ``tf.argmax``/``np.argmax``)."""

@@ -208,7 +208,13 @@ class DataParallelPipeline:
         dev = engine.device
         self.dev = dev
         self.cuda = dev.type == "cuda"
-        shape = (self.B, cam_h, cam_w, 3)
+        # staging holds what the sources deliver: BGR, or the packed 4:2:2 bytes (2 per pixel)
+        # that the engine's first kernel converts (--pixel_format)
+        channels = int(getattr(engine, "frame_channels", 3))
+        if channels != 3 and ingest == "scatter":
+            raise ValueError("ingest='scatter' is not supported with a raw pixel format "
+                             "(--pixel_format yuyv | uyvy): use local ingest")
+        shape = (self.B, cam_h, cam_w, channels)
         self.copy_stream = torch.cuda.Stream(dev) if self.cuda else None
         NS = self.nslots
         self.staging = [torch.zeros(shape, dtype=torch.uint8, device=dev) for _ in range(NS)]

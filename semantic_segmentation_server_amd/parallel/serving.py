@@ -95,7 +95,8 @@ class DistributedServer:
         own = cfg.ingest == "local" or self.ctx.is_root
         self.sources = [make_source(cfg.source, me * S_ + s, cfg.camera_idx,
                                     cfg.camera_width, cfg.camera_height, cfg.source_path,
-                                    fps=cfg.fps_limit, seed=cfg.seed) for s in range(S_)] if own else []
+                                    fps=cfg.fps_limit, seed=cfg.seed, pixel_format=cfg.pixel_format)
+                        for s in range(S_)] if own else []
         res = (cfg.camera_width, cfg.camera_height) if not self.sources else self.sources[0].resolution
         self.camera_res = res
         self.engine = Engine(cfg, self.ctx.device)

@@ -2,6 +2,10 @@
 and the static outputs they write (``labels``; ``post``: packed records or None; ``mask``:
 --serve_masks run words or None). ``replay()`` issues that form's replays, waits and event
 records; after ``consumed`` the buffer may be refilled (None: the model ran on the caller's stream).
+
+With a raw pixel format (``eng.frame_channels == 2``) the frame buffer holds packed 4:2:2 bytes
+and every step owns ``bgr``, the BGR frames its model reads: the conversion is the first kernel
+of the step's model graph, on the model's stream. ``bgr`` is None with BGR ingest (no kernel).
 """
 from __future__ import annotations
 
@@ -42,7 +46,8 @@ class WholeStep:
 
     def __init__(self, eng, frames):
         self.frames, self.consumed = frames, None
-        self.graph, (self.labels, self.post, self.mask) = _graph(lambda: eng._step_outputs(frames))
+        self.bgr = bgr = eng.bgr_buffer(frames)
+        self.graph, (self.labels, self.post, self.mask) = _graph(lambda: eng._step_outputs(frames, bgr))
 
     def replay(self) -> None:
         self.graph.replay()
@@ -57,13 +62,18 @@ class SplitStep:
         self.frames, self.consumed, self.device = frames, None, dev
         # the model writes the step's own label maps
         self.labels = lab = torch.empty((frames.shape[0], eng.H, eng.W), dtype=torch.uint8, device=dev)
+        self.bgr = bgr = eng.bgr_buffer(frames)  # raw ingest: converted into, then read by segment
+
+        def segment():
+            return hm.segment(eng.to_bgr(frames, out=bgr), eng.lut_x, eng.lut_y, out=lab, part=part)
+
         if eng.slot_parallel:  # SlotStep: this slot's plan copy is built outside capture
-            hm.segment(frames, eng.lut_x, eng.lut_y, out=lab, part=part)
+            segment()
             torch.cuda.synchronize(dev)
         if hm is not None:
-            self.model, _ = _graph(lambda: hm.segment(frames, eng.lut_x, eng.lut_y, out=lab, part=part))
+            self.model, _ = _graph(segment)
         else:
-            self.model, _ = _graph(lambda: lab.copy_(eng._infer_eager(frames)))
+            self.model, _ = _graph(lambda: lab.copy_(eng._infer_eager(frames, bgr)))
         self.post_graph, (self.post, self.mask) = _graph(lambda: eng._post_and_mask(lab))
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
@@ -120,10 +130,12 @@ class PartsStep:
         self.frames, self.consumed, self.device = frames, None, dev
         sls = [slice(i * (B // P), (i + 1) * (B // P)) for i in range(P)]
         self.labels = lab = torch.empty((B, eng.H, eng.W), dtype=torch.uint8, device=dev)
+        self.bgr = bgr = eng.bgr_buffer(frames)  # raw ingest: each part converts its own slice
         self.post = post = torch.zeros((B, 1 + 5 * eng.cfg.max_segments), dtype=torch.float32, device=dev)
         self.mask = mask = torch.zeros((B, 4 + eng.mask_cap), dtype=torch.int32,
                                        device=dev) if eng.mask_cap else None
-        parts = [(lambda i=i, sl=sl: hm.segment(frames[sl], eng.lut_x, eng.lut_y, out=lab[sl], part=i),
+        parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
+                                                eng.lut_x, eng.lut_y, out=lab[sl], part=i),
                   lambda sl=sl: eng._device_post(lab[sl], out=post[sl],
                                                  mask_out=mask[sl] if mask is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)

@@ -4,6 +4,7 @@ Replaces the reference's ``BasicEngine`` (``sem_seg_server.py:18,139,162,264``) 
 the per-frame host post-processing (``:164-192``). One ``Engine`` owns one device:
 
     uint8 BGR camera frames (B, Hc, Wc, 3)
+      [--pixel_format yuyv | uyvy: packed 4:2:2 frames (B, Hc, Wc, 2) -> BGR first]
       -> letterbox/normalise (+ stem conv, fused on the HIP path)
       -> DeepLabv3 backbone + ASPP + logits
       -> bilinear upsample + argmax -> (B, H, W) uint8 labels
@@ -122,6 +123,10 @@ class Engine:
             MR.check_geometry(self.W, self.H, self.mask_cap)  # every crop is within H x W
         self.mask_packed: Optional[torch.Tensor] = None
         self.masks: Optional[np.ndarray] = None
+        # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
+        # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
+        self.pixel_format = cfg.pixel_format
+        self.frame_channels = cfg.frame_channels
         if self.backend == "torch":
             self.model = self.model.to(self.device, self.dtype)
             if self.is_cuda:
@@ -171,7 +176,40 @@ class Engine:
         self._bound_graphs = {}  # like the bound buffers' steps
 
     # -------------------------------------------------------------- inference
-    def _infer_eager(self, frames: torch.Tensor) -> torch.Tensor:
+    def to_bgr(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The BGR frames of ``frames`` as ingested: themselves with ``pixel_format`` bgr;
+        else their BT.601 conversion -- the gfx950 kernel on the HIP backend (into ``out``,
+        a captured step's own buffer, if given), the torch definition otherwise."""
+        if self.frame_channels == 3:
+            return frames
+        if frames.dim() != 4 or frames.shape[-1] != 2:
+            raise ValueError(f"pixel_format {self.pixel_format}: frames must be (B, Hc, Wc, 2), "
+                             f"got {tuple(frames.shape)}")
+        uyvy = self.pixel_format == "uyvy"
+        if self.backend == "hip":
+            from ..ops import hip_ops
+            return hip_ops.yuv422_to_bgr(frames, self.bgr_buffer(frames) if out is None else out, uyvy=uyvy)
+        bgr = R.yuv422_to_bgr(frames, uyvy=uyvy)
+        return bgr if out is None else out.copy_(bgr)
+
+    def bgr_buffer(self, frames: torch.Tensor) -> Optional[torch.Tensor]:
+        """A captured step's own BGR buffer for ``frames`` (None with ``pixel_format`` bgr)."""
+        if self.frame_channels == 3:
+            return None
+        return torch.empty(tuple(frames.shape[:3]) + (3,), dtype=torch.uint8, device=frames.device)
+
+    def _host_bgr(self, frame: np.ndarray) -> np.ndarray:
+        """One host frame as BGR (the debug dump's image), by the host conversion."""
+        if self.frame_channels == 3:
+            return frame
+        from ..ops.native import host
+        h, w = frame.shape[:2]
+        return host().yuv422_to_bgr(np.ascontiguousarray(frame).reshape(h, 2 * w),
+                                    self.pixel_format == "uyvy")
+
+    def _infer_eager(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Label maps of frames as ingested; ``bgr``: where a raw format's BGR frames go."""
+        frames = self.to_bgr(frames, out=bgr)
         if self.backend == "hip":
             return self._hip_model.segment(frames, self.lut_x, self.lut_y)
         x = R.preprocess(frames, self.lut_x, self.lut_y,
@@ -213,9 +251,9 @@ class Engine:
             MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
         return out
 
-    def _step_outputs(self, frames: torch.Tensor):
+    def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
         """One eager step: (labels, packed records or None, mask run words or None)."""
-        labels = self._infer_eager(frames)
+        labels = self._infer_eager(frames, bgr)
         if self._use_device_post():
             return (labels, *self._post_and_mask(labels))
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
@@ -335,7 +373,8 @@ class Engine:
         return None if i is None else self.slot_streams[i]
 
     def run_device(self, frames: torch.Tensor):
-        """frames: (B, Hc, Wc, 3) uint8 on this device -> (labels, device post outputs).
+        """frames: (B, Hc, Wc, 3) uint8 on this device (raw pixel formats: (B, Hc, Wc, 2))
+        -> (labels, device post outputs).
 
         With ``cfg.graph`` the step is captured on first use per (B, camera) and
         replayed; outputs then live in static buffers overwritten by the next call.
@@ -348,7 +387,8 @@ class Engine:
         if step is None:  # the engine's own static input buffer, for this batch size
             step, B = self._static_step, frames.shape[0]
             if step is None or step.frames.shape[0] != B:
-                buf = torch.zeros((B, self.cam[1], self.cam[0], 3), dtype=torch.uint8, device=self.device)
+                buf = torch.zeros((B, self.cam[1], self.cam[0], self.frame_channels), dtype=torch.uint8,
+                                  device=self.device)
                 step = self._static_step = capture(self, buf)
             step.frames.copy_(frames, non_blocking=True)
         step.replay()
@@ -392,7 +432,11 @@ class Engine:
 
     def step(self, frames_host: np.ndarray, frame_ids: Sequence[int], ts: Sequence[float],
              streams=0) -> np.ndarray:
-        """Full step from host frames to records (used by the server producer)."""
+        """Full step from host frames ((B, Hc, Wc, 3) BGR; raw pixel formats: (B, Hc, Wc, 2)
+        packed bytes) to records (used by the server producer)."""
+        if frames_host.ndim != 4 or frames_host.shape[-1] != self.frame_channels:
+            raise ValueError(f"pixel_format {self.pixel_format}: frames must be (B, Hc, Wc, "
+                             f"{self.frame_channels}), got {tuple(frames_host.shape)}")
         Hc, Wc = frames_host.shape[1:3]
         self.set_camera(Wc, Hc)
         if not self.is_cuda:
@@ -400,7 +444,7 @@ class Engine:
             with torch.no_grad():
                 labels = self._infer_eager(frames)
             if self.debug is not None and self.debug.want():
-                self.debug.dump(frames_host[0], labels[0].numpy(), self.crop_w, self.crop_h,
+                self.debug.dump(self._host_bgr(frames_host[0]), labels[0].numpy(), self.crop_w, self.crop_h,
                                 _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))
             if self.mask_cap:
                 self.masks = self.host_masks(labels)
@@ -424,7 +468,7 @@ class Engine:
         if self.mask_cap and post is None:
             self.masks = self.host_masks(labels)
         if self.debug is not None and self.debug.want():
-            self.debug.dump(frames_host[0], labels[0].cpu().numpy(), self.crop_w, self.crop_h,
+            self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))
         if recs is None:
             with tr.stage("host_post"):

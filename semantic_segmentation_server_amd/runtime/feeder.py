@@ -39,7 +39,7 @@ log = logging.getLogger(__name__)
 @dataclass
 class Batch:
     slot: int
-    frames: torch.Tensor          # (n, H, W, 3) uint8, pinned when CUDA is available
+    frames: torch.Tensor          # (n, H, W, 3 | 2) uint8, pinned when CUDA is available
     ids: List[int] = field(default_factory=list)
     ts: List[float] = field(default_factory=list)
     streams: List[int] = field(default_factory=list)
@@ -66,7 +66,14 @@ class BatchFeeder(threading.Thread):
         w, h = self.sources[0].resolution
         if any(s.resolution != (w, h) for s in self.sources):
             raise ValueError("all streams of one feeder must share a resolution")
-        self.shape = (self.batch, h, w, 3)
+        # the ring holds what the sources deliver: BGR (3 bytes per pixel), or with a raw
+        # pixel format the packed 4:2:2 bytes (2), which the engine converts on the device
+        from .sources import frame_channels
+        self.pixel_format = getattr(self.sources[0], "pixel_format", "bgr")
+        if any(getattr(s, "pixel_format", "bgr") != self.pixel_format for s in self.sources):
+            raise ValueError("all streams of one feeder must share a pixel format, got "
+                             + ", ".join(sorted({getattr(s, "pixel_format", "bgr") for s in self.sources})))
+        self.shape = (self.batch, h, w, frame_channels(self.pixel_format))
         pin = torch.cuda.is_available() if pin is None else pin
         self.bufs = [torch.empty(self.shape, dtype=torch.uint8, pin_memory=pin) for _ in range(ring)]
         self._free: "queue.Queue[int]" = queue.Queue()

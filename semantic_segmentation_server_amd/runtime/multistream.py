@@ -36,6 +36,8 @@ class StreamGroup:
             self.engines.append(Engine(cfg, device, model=model))
         self.streams = [e.stream for e in self.engines]
         self.backend = self.engines[0].backend
+        self.pixel_format = self.engines[0].pixel_format  # what the staging slots hold
+        self.frame_channels = self.engines[0].frame_channels
         self._out = {}
         # what the pipeline reads of an engine; bind_inputs decides the first two
         self._split = False

@@ -39,6 +39,11 @@ class Producer(threading.Thread):
         super().__init__(name="producer", daemon=True)
         self.engine = engine
         self.sources = sources
+        # the sources deliver what the engine ingests (--pixel_format): BGR, or raw 4:2:2 bytes
+        fmt = getattr(engine, "pixel_format", "bgr")
+        bad = sorted({getattr(s, "pixel_format", "bgr") for s in sources} - {fmt})
+        if bad:
+            raise ValueError(f"the engine ingests pixel_format {fmt}, the sources deliver {', '.join(bad)}")
         self.hub = hub
         self.metrics = metrics
         self.batch = max(1, int(batch))

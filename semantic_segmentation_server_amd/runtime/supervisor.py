@@ -330,7 +330,8 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     engine = Engine(cfg, device)
     S = max(1, cfg.streams)
     sources = [make_source(cfg.source, rank * S + s, cfg.camera_idx, cfg.camera_width, cfg.camera_height,
-                           cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank)
+                           cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank,
+                           pixel_format=cfg.pixel_format)
                for s in range(S)]
     prod = Producer(engine, sources, _RingHub(ring, masks), metrics, cfg.batch, max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
@@ -418,7 +419,8 @@ class SupervisedServer:
         self.metrics = Metrics()
         self.hub = ResultHub(self.nw * self.S, cfg.buffer_max)
         self.camera_res = probe_resolution(cfg.source, cfg.camera_idx, cfg.camera_width,
-                                           cfg.camera_height, cfg.source_path)
+                                           cfg.camera_height, cfg.source_path,
+                                           pixel_format=cfg.pixel_format)
         self.grpc_server, self.port = S.make_server(cfg.max_workers, cfg.port, cfg.host)
         labels = load_labels(cfg.labels)
         S.add_v1_servicer(S.SemanticSegmentationServicer(self.hub, labels, cfg.num_detections,

@@ -43,14 +43,16 @@ class Server:
         self.labels = load_labels(cfg.labels)
         self.hub = ResultHub(cfg.streams, cfg.buffer_max)
         self.camera_res = probe_resolution(cfg.source, cfg.camera_idx, cfg.camera_width,
-                                           cfg.camera_height, cfg.source_path)
+                                           cfg.camera_height, cfg.source_path,
+                                           pixel_format=cfg.pixel_format)
         self.engine = engine or Engine(cfg)
         from .utils.tracing import Tracer
         self.tracer = Tracer(self.metrics, enabled=cfg.profile)
         self.engine.tracer = self.tracer
         self.sources = [make_source(cfg.source, s, cfg.camera_idx, cfg.camera_width,
                                     cfg.camera_height, cfg.source_path, fps=cfg.fps_limit,
-                                    seed=cfg.seed) for s in range(cfg.streams)]
+                                    seed=cfg.seed, pixel_format=cfg.pixel_format)
+                        for s in range(cfg.streams)]
         self.producer = Producer(self.engine, self.sources, self.hub, self.metrics, cfg.batch,
                                  max_steps=max_steps)
         self.grpc_server, self.port = S.make_server(cfg.max_workers, cfg.port, cfg.host)
