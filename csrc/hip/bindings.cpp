@@ -151,8 +151,10 @@ PYBIND11_MODULE(_hip, m) {
   m.def("fused_ir_slice",
         [](uintptr_t in, uintptr_t blob, uintptr_t out, int B, int IH, int IW, int Cin, int OH, int OW,
            int Cout, int hidP, int stride, int residual, int R, int o_be, int o_wd, int o_bd, int o_wp,
-           int o_bp, int nw, uintptr_t stream, int one_barrier) {
+           int o_bp, int nw, uintptr_t stream, int one_barrier, uintptr_t lut_y, int H, int rf_s,
+           int rf_a, int rf_b) {
           FusedBandParams p;
+          p.lut_y = P<const int32_t>(lut_y); p.H = H; p.rf_s = rf_s; p.rf_a = rf_a; p.rf_b = rf_b;
           p.in = P<const bf16>(in); p.blob = P<const void>(blob); p.out = P<bf16>(out);
           p.B = B; p.IH = IH; p.IW = IW; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout;
           p.hidP = hidP; p.stride = stride; p.residual = residual; p.R = R;
@@ -162,7 +164,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("in"), py::arg("blob"), py::arg("out"), py::arg("B"), py::arg("IH"), py::arg("IW"),
         py::arg("Cin"), py::arg("OH"), py::arg("OW"), py::arg("Cout"), py::arg("hidP"), py::arg("stride"),
         py::arg("residual"), py::arg("R"), py::arg("o_be"), py::arg("o_wd"), py::arg("o_bd"),
-        py::arg("o_wp"), py::arg("o_bp"), py::arg("nw"), py::arg("stream"), py::arg("one_barrier") = 0);
+        py::arg("o_wp"), py::arg("o_bp"), py::arg("nw"), py::arg("stream"), py::arg("one_barrier") = 0,
+        py::arg("lut_y") = 0, py::arg("H") = 0, py::arg("rf_s") = 0, py::arg("rf_a") = 0, py::arg("rf_b") = 0);
   m.def("fused_ir_slice_lds", &fused_ir_slice_lds, py::arg("stride"), py::arg("hidP"), py::arg("OW"),
         py::arg("Cout"), py::arg("nw"), py::arg("one_barrier") = false);
   m.def("fused_ir_band_lds", &fused_ir_band_lds, py::arg("stride"), py::arg("hidP"), py::arg("OW"),
@@ -184,8 +187,10 @@ PYBIND11_MODULE(_hip, m) {
   m.def("stem_band",
         [](uintptr_t frames, uintptr_t lx, uintptr_t ly, uintptr_t ws, uintptr_t bs, uintptr_t wd,
            uintptr_t bd, uintptr_t wp, uintptr_t bp, uintptr_t out, int B, int Hc, int Wc, int H,
-           int W, int SH, int SW, int R, int nbx, uintptr_t stream, int one_barrier) {
+           int W, int SH, int SW, int R, int nbx, uintptr_t stream, int one_barrier, int rf_s, int rf_a,
+           int rf_b) {
           StemBlock0Params p;
+          p.rf_s = rf_s; p.rf_a = rf_a; p.rf_b = rf_b;
           p.frames = P<const uint8_t>(frames); p.lut_x = P<const int32_t>(lx); p.lut_y = P<const int32_t>(ly);
           p.ws = P<const bf16>(ws); p.bs = P<const float>(bs); p.wd = P<const void>(wd);
           p.bd = P<const void>(bd); p.wp = P<const void>(wp); p.bp = P<const float>(bp); p.out = P<bf16>(out);
@@ -196,7 +201,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("frames"), py::arg("lx"), py::arg("ly"), py::arg("ws"), py::arg("bs"), py::arg("wd"),
         py::arg("bd"), py::arg("wp"), py::arg("bp"), py::arg("out"), py::arg("B"), py::arg("Hc"),
         py::arg("Wc"), py::arg("H"), py::arg("W"), py::arg("SH"), py::arg("SW"), py::arg("R"),
-        py::arg("nbx"), py::arg("stream"), py::arg("one_barrier") = 1);
+        py::arg("nbx"), py::arg("stream"), py::arg("one_barrier") = 1, py::arg("rf_s") = 0,
+        py::arg("rf_a") = 0, py::arg("rf_b") = 0);
   m.def("stem_band_lds", &stem_band_lds, py::arg("SW"), py::arg("nbx"), py::arg("R"));
 
   m.def("aspp_head",

@@ -160,6 +160,12 @@ struct FusedBandParams {
   int R = 8, nslot = 2, blob_bytes = 0, o_be = 0, o_wd = 0, o_bd = 0, o_wp = 0, o_bp = 0;
   int hs = 1;                 // 2: two waves per column group, each half the hidden channels
   int split = 1;              // 2: two column bands across the map width
+  // fused_ir_slice only -- the letterbox's constant rows computed once (row_repeat.h):
+  // lut_y [H] is the model-input row LUT in use (nullptr: off), (rf_s, rf_a, rf_b) the
+  // cumulative vertical receptive field of this block's output rows: output row o reads
+  // model-input rows [rf_s o - rf_a, rf_s o + rf_b]
+  const int32_t* lut_y = nullptr;
+  int H = 0, rf_s = 0, rf_a = 0, rf_b = 0;
 };
 void fused_ir_band(const FusedBandParams& p, hipStream_t s);
 size_t fused_ir_band_lds(int stride, int hidP, int OW, int blob_bytes, int nslot, int hs = 1, int Cout = 0,
@@ -180,6 +186,9 @@ struct StemBlock0Params {
   const void* wd = nullptr; const void* bd = nullptr; const void* wp = nullptr;
   const float* bp = nullptr; bf16* out = nullptr;
   int B = 0, Hc = 0, Wc = 0, H = 0, W = 0, SH = 0, SW = 0, Cout = 16, TY = 8, TX = 16;
+  // stem_band only -- the receptive field of the output rows in model-input rows, (2, 3, 3)
+  // for stem + block 0 (row_repeat.h; rf_s 0: every row computed)
+  int rf_s = 0, rf_a = 0, rf_b = 0;
 };
 void stem_block0(const StemBlock0Params& p, hipStream_t s);
 // Row-streaming stem + block 0 (stem_band.hip): bands of p.TY output rows x ceil(SW / nbx)

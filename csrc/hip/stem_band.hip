@@ -30,6 +30,7 @@
 // (/root/reference/sem_seg_server.py:151-162: BGR->RGB, NEAREST letterbox, quantised input).
 #include "common.h"
 #include "kernels.h"
+#include "row_repeat.h"
 
 namespace ssa {
 
@@ -45,6 +46,7 @@ struct StemBandArgs {
   const bf16* ws; const float* bs; const f16* wd; const f16* bd; const f16* wp; const float* bp;
   bf16* out;
   int B, Hc, Wc, H, W, SH, SW, R, nbx, nby, TW;
+  int rf_s, rf_a, rf_b;  // output rows' receptive field in model-input rows (rf_s 0: no row repeat)
 };
 
 __device__ __forceinline__ void lds_barrier() {
@@ -72,14 +74,11 @@ __global__ __launch_bounds__(64 * NW) void stem_band_kernel(StemBandArgs a) {
   blk /= a.nbx;
   const int by = blk % a.nby;
   const int b = blk / a.nby;
-  const int x0 = bx * a.TW, y0 = by * a.R, y1 = min(y0 + a.R, a.SH);
+  const int x0 = bx * a.TW;
   const int twv = min(a.TW, a.SW - x0);
   const int NSC = twv + 2;            // stem columns: global x0 - 1 .. x0 + twv
   const int NIC = 2 * NSC + 1;        // input columns: global 2 x0 - 3 .. 2 (x0 + twv) + 1
   const int ixb = 2 * x0 - 3;
-  const int rbase = 2 * y0 - 3;       // global input row of ring row 0 (stem row y0 - 1 reads 2y0-3..2y0-1)
-  const int n_st = y1 - y0 + 2;       // stem rows y0 - 1 .. y1
-  const int n_rows = 2 * n_st + 1;    // input rows the band reads
 
   // LDS: [IN ring 6 rows][NIC][8 B] | [S rows 2 x NSC x 80 B] | [lut_y of the band's rows]
   bf16* IN = reinterpret_cast<bf16*>(smem);
@@ -87,10 +86,6 @@ __global__ __launch_bounds__(64 * NW) void stem_band_kernel(StemBandArgs a) {
   char* S2 = smem + (size_t)6 * NIC * 8;
   const int s_bytes = NSC * kSP;
   int* sly = reinterpret_cast<int*>(S2 + (size_t)2 * s_bytes);
-  for (int i = tid; i < n_rows; i += NT) {
-    const int r = rbase + i;
-    sly[i] = (r >= 0 && r < a.H) ? a.lut_y[r] : -2;  // -2: outside the model input (conv zero pad)
-  }
 
   // ---- weights -> VGPRs
   s16x4 wst[2][3];
@@ -109,6 +104,12 @@ __global__ __launch_bounds__(64 * NW) void stem_band_kernel(StemBandArgs a) {
   const f16x8 af = *reinterpret_cast<const f16x8*>(a.wp + (size_t)r16 * 32 + kq * 8);
   const f32x4 bpv = *reinterpret_cast<const f32x4*>(a.bp + kq * 4);
 
+  // ---- the constant letterbox rows (row_repeat.h): output rows zn.z0 + 1 .. zn.z0 + zn.nrep
+  // equal row zn.z0; the band's rows come from the compressed row space, as <= 2 segments
+  RowZone zn{-1, 0};
+  if (a.rf_s > 0) zn = row_zone(pad_start(a.lut_y, a.H, lane), a.H, a.SH, a.rf_s, a.rf_a, a.rf_b);
+  const BandSegs segs = band_segments(zn, a.SH, a.R, a.nby, by);
+
   // ---- gather lanes: pixel p = tid + u * NT of a row pair -> (row k, local input col i)
   const uint8_t* fb = a.frames + (size_t)b * a.Hc * a.Wc * 3;
   int gk[GPX], gi[GPX], gsx[GPX];  // row in pair, local col, camera col (-1 pad, -2 outside)
@@ -121,58 +122,6 @@ __global__ __launch_bounds__(64 * NW) void stem_band_kernel(StemBandArgs a) {
     const int x = ixb + gi[u];
     gsx[u] = (live && x >= 0 && x < a.W) ? a.lut_x[x] : -2;
   }
-  __syncthreads();  // sly visible
-
-  // camera bytes of one pixel: -> bf16 RGB0 (x / 127.5 - 1, BGR -> RGB; -1 letterbox pad,
-  // 0 outside the model input)
-  struct Px { uint32_t c0, c1, c2; int kind; };
-  // branch-free: every lane loads a (clamped) pixel, the kind selects at store time (a
-  // conditional load makes the compiler wait for it right away)
-  auto fetch_px = [&](int rel_row, int u) -> Px {
-    const int sy = sly[min(rel_row, n_rows - 1)];
-    const int sx = gsx[u];
-    Px v;
-    v.kind = (gk[u] > 1 || rel_row >= n_rows || sy == -2 || sx == -2) ? -2 : (sy < 0 || sx < 0) ? -1 : 0;
-    // 32-bit byte offset from the uniform frame base (a frame is < 4 GiB): SGPR base +
-    // VGPR offset addressing, no 64-bit multiply-add per pixel
-    const uint8_t* px = fb + (unsigned)((max(sy, 0) * a.Wc + max(sx, 0)) * 3);
-    v.c0 = px[0]; v.c1 = px[1]; v.c2 = px[2];
-    return v;
-  };
-  // off: the pixel's element offset in the ring (-1: ring row rel_row % 6 computed here)
-  auto store_px = [&](int rel_row, int u, const Px& v, int off = -1) {
-    if (gk[u] > 1 || rel_row >= n_rows) return;
-    float rgb[3] = {0.f, 0.f, 0.f};
-    if (v.kind == 0) {
-      rgb[0] = v.c2 * (1.f / 127.5f) - 1.f;
-      rgb[1] = v.c1 * (1.f / 127.5f) - 1.f;
-      rgb[2] = v.c0 * (1.f / 127.5f) - 1.f;
-    } else if (v.kind == -1) {
-      rgb[0] = rgb[1] = rgb[2] = -1.f;
-    }
-    const bf16x4 o = {(bf16)rgb[0], (bf16)rgb[1], (bf16)rgb[2], (bf16)0.f};
-    *reinterpret_cast<bf16x4*>(IN + (off >= 0 ? off : (rel_row % 6) * in_row + gi[u] * 4)) = o;
-  };
-  // row pair q = ring rows 2q + 1, 2q + 2 (step q's new rows; step 0 also reads row 0)
-  Px xr[PD][GPX];
-  // prologue: rows 0, 1, 2 now; pairs 1..PD in flight
-  {
-    Px r0[GPX], p0[GPX];
-#pragma unroll
-    for (int u = 0; u < GPX; ++u) {
-      r0[u] = fetch_px(gk[u], u);          // rows 0 and 1 (k = 0, 1)
-      p0[u] = fetch_px(2 + gk[u], u);      // rows 2 and 3 (row 3 = pair 1's first row)
-    }
-#pragma unroll
-    for (int u = 0; u < GPX; ++u) {
-      store_px(gk[u], u, r0[u]);
-      if (gk[u] == 0) store_px(2, u, p0[u]);  // row 2 (pair 0's second row)
-    }
-  }
-#pragma unroll
-  for (int q = 1; q <= PD; ++q)
-#pragma unroll
-    for (int u = 0; u < GPX; ++u) xr[q % PD][u] = fetch_px(2 * q + 1 + gk[u], u);
 
   // ---- this lane's stem column (stem phase) and output column (depthwise phase)
   const int sj = g * 16 + r16;                // local stem column
@@ -210,74 +159,152 @@ __global__ __launch_bounds__(64 * NW) void stem_band_kernel(StemBandArgs a) {
   // f32 -> f16 conversion and the last fma (48 of the unrolled loop's ~360 VALU were min / max)
   const f16x4 z4 = {0, 0, 0, 0}, s4 = {1, 1, 1, 1};
   const f16x8 h0 = {0, 0, 0, 0, 0, 0, 0, 0}, h6 = {1, 1, 1, 1, 1, 1, 1, 1};
-  f16x8 D[3];
-#pragma unroll
-  for (int s_ = 0; s_ < 3; ++s_) D[s_] = bdv;
-  __syncthreads();  // prologue rows visible
 
-  for (int t0 = 0; t0 < n_st; t0 += U) {
-#pragma unroll
-    for (int ph = 0; ph < U; ++ph) {
-      const int t = t0 + ph;
-      const int s = y0 - 1 + t;  // stem row (global)
-      // ---- [gather] the next step's rows (pair t + 1) -> IN; its registers refill
-      // with pair t + 1 + PD
-      {
-        const int sl = (ph + 1) % PD;
-#pragma unroll
-        for (int u = 0; u < GPX; ++u) store_px(2 * (t + 1) + 1 + gk[u], u, xr[sl][u], sto[ph][u]);
-#pragma unroll
-        for (int u = 0; u < GPX; ++u) xr[sl][u] = fetch_px(2 * (t + 1 + PD) + 1 + gk[u], u);
+  // ---- the streaming body, once per segment of the band's rows
+  bool again = false;  // a segment ran before this one: its global stores may be pending
+#pragma clang loop unroll(disable)
+  for (int seg = 0; seg < 2; ++seg) {
+    const int y0 = seg == 0 ? segs.y0[0] : segs.y0[1];
+    const int y1 = seg == 0 ? segs.y1[0] : segs.y1[1];
+    if (y0 >= y1) continue;            // uniform
+    const int rbase = 2 * y0 - 3;      // global input row of ring row 0 (stem row y0 - 1 reads 2y0-3..2y0-1)
+    const int n_st = y1 - y0 + 2;      // stem rows y0 - 1 .. y1
+    const int n_rows = 2 * n_st + 1;   // input rows the segment reads
+    // LDS hand-offs only after the first segment: a full __syncthreads() would wait for its
+    // output stores
+    if (again) lds_barrier();  // the previous segment's last reads of sly / IN / S are done
+    for (int i = tid; i < n_rows; i += NT) {
+      const int r = rbase + i;
+      sly[i] = (r >= 0 && r < a.H) ? a.lut_y[r] : -2;  // -2: outside the model input (conv zero pad)
+    }
+    if (again) lds_barrier();
+    else __syncthreads();  // sly visible
+
+    // camera bytes of one pixel: -> bf16 RGB0 (x / 127.5 - 1, BGR -> RGB; -1 letterbox pad,
+    // 0 outside the model input)
+    struct Px { uint32_t c0, c1, c2; int kind; };
+    // branch-free: every lane loads a (clamped) pixel, the kind selects at store time (a
+    // conditional load makes the compiler wait for it right away)
+    auto fetch_px = [&](int rel_row, int u) -> Px {
+      const int sy = sly[min(rel_row, n_rows - 1)];
+      const int sx = gsx[u];
+      Px v;
+      v.kind = (gk[u] > 1 || rel_row >= n_rows || sy == -2 || sx == -2) ? -2 : (sy < 0 || sx < 0) ? -1 : 0;
+      // 32-bit byte offset from the uniform frame base (a frame is < 4 GiB): SGPR base +
+      // VGPR offset addressing, no 64-bit multiply-add per pixel
+      const uint8_t* px = fb + (unsigned)((max(sy, 0) * a.Wc + max(sx, 0)) * 3);
+      v.c0 = px[0]; v.c1 = px[1]; v.c2 = px[2];
+      return v;
+    };
+    // off: the pixel's element offset in the ring (-1: ring row rel_row % 6 computed here)
+    auto store_px = [&](int rel_row, int u, const Px& v, int off = -1) {
+      if (gk[u] > 1 || rel_row >= n_rows) return;
+      float rgb[3] = {0.f, 0.f, 0.f};
+      if (v.kind == 0) {
+        rgb[0] = v.c2 * (1.f / 127.5f) - 1.f;
+        rgb[1] = v.c1 * (1.f / 127.5f) - 1.f;
+        rgb[2] = v.c0 * (1.f / 127.5f) - 1.f;
+      } else if (v.kind == -1) {
+        rgb[0] = rgb[1] = rgb[2] = -1.f;
       }
-      // ---- [stem] row s from ring rows 2t .. 2t + 2 -> S[t & 1] (fp16, relu6; 0 outside)
-      char* S = S2 + (t & 1) * s_bytes;
-      const bool srow = s >= 0 && s < a.SH && t < n_st;  // uniform
-      {
-        s16x4 xf[3];
+      const bf16x4 o = {(bf16)rgb[0], (bf16)rgb[1], (bf16)rgb[2], (bf16)0.f};
+      *reinterpret_cast<bf16x4*>(IN + (off >= 0 ? off : (rel_row % 6) * in_row + gi[u] * 4)) = o;
+    };
+    // row pair q = ring rows 2q + 1, 2q + 2 (step q's new rows; step 0 also reads row 0)
+    Px xr[PD][GPX];
+    // prologue: rows 0, 1, 2 now; pairs 1..PD in flight
+    {
+      Px r0[GPX], p0[GPX];
 #pragma unroll
-        for (int m = 0; m < 3; ++m)
-          xf[m] = *reinterpret_cast<const s16x4*>(IN + sro[ph][m]);
+      for (int u = 0; u < GPX; ++u) {
+        r0[u] = fetch_px(gk[u], u);          // rows 0 and 1 (k = 0, 1)
+        p0[u] = fetch_px(2 + gk[u], u);      // rows 2 and 3 (row 3 = pair 1's first row)
+      }
 #pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-          f32x4 e4 = bst[sub];
+      for (int u = 0; u < GPX; ++u) {
+        store_px(gk[u], u, r0[u]);
+        if (gk[u] == 0) store_px(2, u, p0[u]);  // row 2 (pair 0's second row)
+      }
+    }
 #pragma unroll
-          for (int m = 0; m < 3; ++m) e4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wst[sub][m], xf[m], e4, 0, 0, 0);
-          f16x4 o = {(f16)e4[0], (f16)e4[1], (f16)e4[2], (f16)e4[3]};
-          o = __builtin_elementwise_min(__builtin_elementwise_max(o, z4), s4);
-          if (!(srow && sin_x)) o = z4;  // depthwise zero padding outside the stem image
-          if (sj < NSC) *reinterpret_cast<f16x4*>(S + (size_t)sj * kSP + (sub * 16 + kq * 4) * 2) = o;
+    for (int q = 1; q <= PD; ++q)
+#pragma unroll
+      for (int u = 0; u < GPX; ++u) xr[q % PD][u] = fetch_px(2 * q + 1 + gk[u], u);
+
+    f16x8 D[3];
+#pragma unroll
+    for (int s_ = 0; s_ < 3; ++s_) D[s_] = bdv;
+    if (again) lds_barrier();
+    else __syncthreads();  // prologue rows visible
+    again = true;
+
+    for (int t0 = 0; t0 < n_st; t0 += U) {
+#pragma unroll
+      for (int ph = 0; ph < U; ++ph) {
+        const int t = t0 + ph;
+        const int s = y0 - 1 + t;  // stem row (global)
+        // ---- [gather] the next step's rows (pair t + 1) -> IN; its registers refill
+        // with pair t + 1 + PD
+        {
+          const int sl = (ph + 1) % PD;
+#pragma unroll
+          for (int u = 0; u < GPX; ++u) store_px(2 * (t + 1) + 1 + gk[u], u, xr[sl][u], sto[ph][u]);
+#pragma unroll
+          for (int u = 0; u < GPX; ++u) xr[sl][u] = fetch_px(2 * (t + 1 + PD) + 1 + gk[u], u);
         }
-      }
-      lds_barrier();  // A: stem row complete
-      // ---- [depthwise] stem row s feeds output rows s + 1 (ky 0), s (ky 1), s - 1 (ky 2, completes)
-      // slots: output o lives in slot (o - y0 + 1) % 3 (static in the unrolled round)
-      {
-        f16x8 v[3];
+        // ---- [stem] row s from ring rows 2t .. 2t + 2 -> S[t & 1] (fp16, relu6; 0 outside)
+        char* S = S2 + (t & 1) * s_bytes;
+        const bool srow = s >= 0 && s < a.SH && t < n_st;  // uniform
+        {
+          s16x4 xf[3];
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) v[kx] = *reinterpret_cast<const f16x8*>(S + (size_t)(xc + kx) * kSP + kq * 16);
-        const int s0 = (ph + 1) % 3, s1 = ph % 3, s2 = (ph + 2) % 3;  // o = s+1, s, s-1
+          for (int m = 0; m < 3; ++m)
+            xf[m] = *reinterpret_cast<const s16x4*>(IN + sro[ph][m]);
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) D[s0] = v[kx] * wdv[kx] + D[s0];
+          for (int sub = 0; sub < 2; ++sub) {
+            f32x4 e4 = bst[sub];
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) D[s1] = v[kx] * wdv[3 + kx] + D[s1];
-#pragma unroll
-        for (int kx = 0; kx < 3; ++kx) D[s2] = v[kx] * wdv[6 + kx] + D[s2];
-        const int o = s - 1;
-        if (o >= y0 && o < y1) {  // uniform
-          f16x8 d = __builtin_elementwise_min(__builtin_elementwise_max(D[s2], h0), h6);
-          f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-          acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, d, acc, 0, 0, 0);
-          if (xv) {
-            bf16* orow = a.out + ((size_t)b * a.SH + o) * a.SW * 16;  // uniform
-            bf16* op = reinterpret_cast<bf16*>(reinterpret_cast<char*>(orow) + (unsigned)(((x0 + xl) * 16 + kq * 4) * 2));
-            const bf16x4 ob = {(bf16)(acc[0] + bpv[0]), (bf16)(acc[1] + bpv[1]), (bf16)(acc[2] + bpv[2]),
-                               (bf16)(acc[3] + bpv[3])};
-            *reinterpret_cast<bf16x4*>(op) = ob;
+            for (int m = 0; m < 3; ++m) e4 = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(wst[sub][m], xf[m], e4, 0, 0, 0);
+            f16x4 o = {(f16)e4[0], (f16)e4[1], (f16)e4[2], (f16)e4[3]};
+            o = __builtin_elementwise_min(__builtin_elementwise_max(o, z4), s4);
+            if (!(srow && sin_x)) o = z4;  // depthwise zero padding outside the stem image
+            if (sj < NSC) *reinterpret_cast<f16x4*>(S + (size_t)sj * kSP + (sub * 16 + kq * 4) * 2) = o;
           }
         }
-        D[s2] = bdv;  // slot reopens as output s + 2 (bias first, as stem_block0_kernel)
+        lds_barrier();  // A: stem row complete
+        // ---- [depthwise] stem row s feeds output rows s + 1 (ky 0), s (ky 1), s - 1 (ky 2, completes)
+        // slots: output o lives in slot (o - y0 + 1) % 3 (static in the unrolled round)
+        {
+          f16x8 v[3];
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) v[kx] = *reinterpret_cast<const f16x8*>(S + (size_t)(xc + kx) * kSP + kq * 16);
+          const int s0 = (ph + 1) % 3, s1 = ph % 3, s2 = (ph + 2) % 3;  // o = s+1, s, s-1
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) D[s0] = v[kx] * wdv[kx] + D[s0];
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) D[s1] = v[kx] * wdv[3 + kx] + D[s1];
+#pragma unroll
+          for (int kx = 0; kx < 3; ++kx) D[s2] = v[kx] * wdv[6 + kx] + D[s2];
+          const int o = s - 1;
+          if (o >= y0 && o < y1) {  // uniform
+            f16x8 d = __builtin_elementwise_min(__builtin_elementwise_max(D[s2], h0), h6);
+            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, d, acc, 0, 0, 0);
+            if (xv) {
+              bf16* orow = a.out + ((size_t)b * a.SH + o) * a.SW * 16;  // uniform
+              const unsigned ooff = ((x0 + xl) * 16 + kq * 4) * 2;
+              const bf16x4 ob = {(bf16)(acc[0] + bpv[0]), (bf16)(acc[1] + bpv[1]), (bf16)(acc[2] + bpv[2]),
+                                 (bf16)(acc[3] + bpv[3])};
+              *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(orow) + ooff) = ob;
+              if (o == zn.z0)  // uniform: the constant rows below are this row
+                for (int r = 1; r <= zn.nrep; ++r)
+                  *reinterpret_cast<bf16x4*>(reinterpret_cast<char*>(orow + (size_t)r * a.SW * 16) + ooff) = ob;
+            }
+          }
+          D[s2] = bdv;  // slot reopens as output s + 2 (bias first, as stem_block0_kernel)
+        }
+        if (!ONEB) lds_barrier();  // two-barrier form (round 4): B, S and IN rows free / visible
       }
-      if (!ONEB) lds_barrier();  // two-barrier form (round 4): B, S and IN rows free / visible
     }
   }
 }
@@ -315,7 +342,8 @@ void stem_band(const StemBlock0Params& p, int nbx, hipStream_t st, bool one_barr
   if (lds > 160 * 1024) throw std::invalid_argument("stem_band: LDS over 160 KiB");
   StemBandArgs a{p.frames, p.lut_x, p.lut_y, p.ws, p.bs, reinterpret_cast<const f16*>(p.wd),
                  reinterpret_cast<const f16*>(p.bd), reinterpret_cast<const f16*>(p.wp), p.bp, p.out,
-                 p.B, p.Hc, p.Wc, p.H, p.W, p.SH, p.SW, p.TY, nbx, cdiv(p.SH, p.TY), TW};
+                 p.B, p.Hc, p.Wc, p.H, p.W, p.SH, p.SW, p.TY, nbx, cdiv(p.SH, p.TY), TW,
+                 p.rf_s, p.rf_a, p.rf_b};
 #define SB(NW_, G_)                                                   \
   if (NW == NW_ && GPX == G_) {                                       \
     if (one_barrier) launch_stem_band<NW_, G_, true>(a, lds, st);     \

@@ -33,6 +33,7 @@ import torch
 from ..ops import fused_band as FB
 from ..ops import fused_span as FS
 from ..ops import hip_ops as K
+from ..ops import row_repeat as RR
 from ..ops.hip_ops import conv_out_hw
 from .deeplab import DeepLabV3
 from .layers import ConvBNAct
@@ -201,6 +202,7 @@ class HipDeepLab(HipPlanModel):
     # ------------------------------------------------------------------ plan
     def _build(self, B: int, Hc: int, Wc: int, buf, bufs):
         mnv2 = self.kind == "mnv2"
+        self._cam = (Hc, Wc)
         ops, st = (self._stem_mnv2 if mnv2 else self._stem_resnet)(B, Hc, Wc, buf, bufs)
         first = 1 if mnv2 and self.stem_block0 is not None else 0  # block 0 is in the stem choice
         for i in range(first, len(self.blocks)):
@@ -269,7 +271,8 @@ class HipDeepLab(HipPlanModel):
                 for oneb in (True, False):
                     bands.setdefault(f"stem_band{R}x{nbx}" + ("" if oneb else "b2"), [
                         lambda frames, lx, ly, R=R, nbx=nbx, oneb=oneb: K.stem_band(
-                            frames, lx, ly, sbp, out0, H=H, W=W, R=R, nbx=nbx, one_barrier=oneb)])
+                            frames, lx, ly, sbp, out0, H=H, W=W, R=R, nbx=nbx, one_barrier=oneb,
+                            row_repeat=self._row_repeat(0, SH, R))])
         # fixed order (pick 0 is the default, the tune file names variants): last band first
         return [Choice("stem+block0", list(bands.items())[::-1] + tiles +
                        [("separate", [stem] + block0)])], st0
@@ -615,6 +618,10 @@ class HipDeepLab(HipPlanModel):
         if blk["expand"] is None:
             return []
         out = []
+        # the letterbox's constant rows computed once: the kernel derives them from the
+        # LUT of the call and this block's receptive field (ops/row_repeat.py); per launch,
+        # where _row_repeat expects it to pay
+        rf = self._block_rf(g.i)
         for nw in FB.slice_widths(s.cin, g.hid, s.cout, s.stride, s.dilation):
             bp_ = self._packed(blk, "band")
             twmax = 16 * nw - (2 if s.stride == 1 else 1)
@@ -626,10 +633,42 @@ class HipDeepLab(HipPlanModel):
                 # workgroups per CU (256 CUs)
                 for R in _rows_per_band(B * nbx * OH, OH, (256, 512, 768, 1024)):
                     out.append((f"slice{R}w{nw}" + ("o" if oneb else ""), [
-                        lambda *_, R=R, nw=nw, bp_=bp_, oneb=oneb: FB.fused_ir_slice(
+                        lambda frames, lx, ly, R=R, nw=nw, bp_=bp_, oneb=oneb,
+                        rr=self._row_repeat(g.i, OH, R, s.stride): FB.fused_ir_slice(
                             g.x, bp_, g.out, B=B, IH=g.h, IW=g.w, stride=s.stride,
-                            residual=s.residual, R=R, nw=nw, one_barrier=oneb)]))
+                            residual=s.residual, R=R, nw=nw, one_barrier=oneb,
+                            lut_y=ly if rr else None, H=self.H, rf=rf)]))
         return out[::-1]  # the last one built is listed first (fixed order: _mnv2_block)
+
+    def _row_repeat(self, i: int, OH: int, R: int, stride: int = 2) -> bool:
+        """Whether a row-streaming launch of block ``i`` (0: stem + block 0) with bands of
+        ``R`` of its ``OH`` rows gets the row repeat. The kernel derives the zone from the LUT
+        of the call; this only decides where finding it is worth its cost, from the
+        letterbox of the plan's camera: on where a band gets shorter (a square or portrait
+        camera, or block 6's 2 of 33 rows at 4:3, would pay the LUT scan for nothing), and
+        in the stride-2 slice blocks only: the stride-1 blocks' time is mostly per-workgroup
+        fixed cost, and block 2 measured no faster with 4 of 17 rows fewer.
+        ``SSA_ROW_REPEAT=all`` turns it on everywhere (tests), ``0`` off."""
+        m, rf = RR.mode(), self._block_rf(i)
+        if m == "off" or rf is None:
+            return False
+        if m == "all":
+            return True
+        from ..ops import reference_ops as R_
+        Hc, Wc = self._cam
+        p0 = RR.pad_start(R_.letterbox_luts(Wc, Hc, self.W, self.H)[1])
+        return stride == 2 and RR.pays(p0, self.H, OH, R, rf)
+
+    def _block_rf(self, i: int) -> Optional[Tuple[int, int, int]]:
+        """The cumulative vertical receptive field of block ``i``'s output rows in
+        model-input rows (ops/row_repeat.py), None where the 3x3 pad-1 chain does not hold."""
+        sk, ss = self.stem[2], self.stem[3]
+        if sk != 3:
+            return None
+        rf = RR.rf_conv3x3(RR.RF_INPUT, ss)
+        for blk in self.blocks[:i + 1]:
+            rf = RR.rf_conv3x3(rf, blk["spec"].stride, blk["spec"].dilation)
+        return rf
 
     def _packed(self, blk: dict, key: str) -> dict:
         """The block's weights in the "span" / "band" kernels' layout, packed on first use."""

@@ -24,7 +24,7 @@ Reference parity: the model being executed is the reference's
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -157,16 +157,25 @@ def slice_lds(packed: Dict, stride: int, OW: int, nw: int, one_barrier: bool = F
 
 def fused_ir_slice(x: torch.Tensor, packed: Dict, out: torch.Tensor, *, B: int, IH: int, IW: int,
                    stride: int, residual: bool, R: int = 8, nw: int = 2,
-                   one_barrier: bool = False) -> torch.Tensor:
+                   one_barrier: bool = False, lut_y: Optional[torch.Tensor] = None, H: int = 0,
+                   rf: Optional[Tuple[int, int, int]] = None) -> torch.Tensor:
     """Launch fused_ir_slice_kernel (csrc/hip/fused_ir_slice.hip): the band kernel's row
     streaming with waves = nw column groups x hidden chunks of 32, each wave's chunk
     weights held in VGPRs. Same blob as fused_ir_band; bit-identical results.
-    ``one_barrier``: one workgroup barrier per input row (E / D rows double-buffered)."""
+    ``one_barrier``: one workgroup barrier per input row (E / D rows double-buffered).
+    ``lut_y`` (int32 [H], the letterbox row LUT of the model input), ``H`` and ``rf`` (the
+    output rows' receptive field in model-input rows, ops/row_repeat.py): the output rows
+    that see only the letterbox's constant rows are computed once and stored repeatedly;
+    the input's rows in that zone must be equal. Default off."""
     from .hip_ops import _chk, _dbg, _hip_mod, _ptr, _stream
     Cin, Cout = packed["Cin"], packed["Cout"]
     OH, OW = (IH - 1) // stride + 1, (IW - 1) // stride + 1
     if residual and (stride != 1 or Cin != Cout):
         raise ValueError("fused_ir_slice: residual needs stride 1 and Cin == Cout")
+    if lut_y is not None:
+        if rf is None or H < 1:
+            raise ValueError("fused_ir_slice: lut_y needs H and rf")
+        _chk(lut_y, torch.int32, "lut_y", H)
     if R < 1 or not slice_supported(Cin, packed["hid"], Cout, stride, 1, nw):
         raise ValueError("fused_ir_slice: no instantiation for this block / width")
     _chk(x, torch.bfloat16, "x", B * IH * IW * Cin)
@@ -177,7 +186,8 @@ def fused_ir_slice(x: torch.Tensor, packed: Dict, out: torch.Tensor, *, B: int, 
     _hip_mod().fused_ir_slice(_ptr(x), _ptr(packed["blob"]), _ptr(out), B, IH, IW, Cin, OH, OW, Cout,
                               packed["hidP"], stride, int(bool(residual)), R, packed["o_be"],
                               packed["o_wd"], packed["o_bd"], packed["o_wp"], packed["o_bp"], nw,
-                              _stream(), int(bool(one_barrier)))
+                              _stream(), int(bool(one_barrier)),
+                              *((_ptr(lut_y), H, *rf) if lut_y is not None else (0, 0, 0, 0, 0)))
     _dbg("fused_ir_slice")
     return out
 

@@ -674,11 +674,15 @@ def stem_block0(frames, lut_x, lut_y, packed: dict, out, *, H, W, tile=(8, 16)):
     return out
 
 
-def stem_band(frames, lut_x, lut_y, packed: dict, out, *, H, W, R=16, nbx=3, one_barrier=True):
+def stem_band(frames, lut_x, lut_y, packed: dict, out, *, H, W, R=16, nbx=3, one_barrier=True,
+              row_repeat=False):
     """Row-streaming stem + block 0 (csrc/hip/stem_band.hip): bands of R output rows x
     ceil(SW / nbx) columns; same weights and bit-identical results as ``stem_block0``.
     ``one_barrier``: one workgroup barrier per stem row (double-buffered stem row; False:
-    the round-4 two-barrier step)."""
+    the round-4 two-barrier step). ``row_repeat``: the output rows that see only the
+    letterbox's constant rows (the trailing -1 run of ``lut_y``) are computed once and stored
+    repeatedly (ops/row_repeat.py)."""
+    from .row_repeat import RF_INPUT, rf_conv3x3
     B, Hc, Wc, _ = frames.shape
     SH, SW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     TW = -(-SW // nbx)
@@ -694,7 +698,9 @@ def stem_band(frames, lut_x, lut_y, packed: dict, out, *, H, W, R=16, nbx=3, one
     P = packed
     _hip_mod().stem_band(_ptr(frames), _ptr(lut_x), _ptr(lut_y), _ptr(P["ws"]), _ptr(P["bs"]),
                          _ptr(P["wd_h"]), _ptr(P["bd_h"]), _ptr(P["wp_h"]), _ptr(P["bp"]),
-                         _ptr(out), B, Hc, Wc, H, W, SH, SW, R, nbx, _stream(), int(bool(one_barrier)))
+                         _ptr(out), B, Hc, Wc, H, W, SH, SW, R, nbx, _stream(), int(bool(one_barrier)),
+                         # stem (3x3 s2) + block 0's depthwise (3x3 s1): (2, 3, 3)
+                         *(rf_conv3x3(rf_conv3x3(RF_INPUT, 2)) if row_repeat else (0, 0, 0)))
     _dbg("stem_band")
     return out
 
