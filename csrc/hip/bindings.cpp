@@ -43,7 +43,7 @@ PYBIND11_MODULE(_hip, m) {
 
   m.def("conv_gemm_grouped",
         [](py::list groups, uintptr_t order, int nblocks, int variant, uintptr_t stream, int ks, uintptr_t part,
-           uintptr_t cnt, int cnt_stride) {
+           uintptr_t cnt, int cnt_stride, py::object pool) {
           // groups: tuples (in, w, bias, img_bias, res, out, B, IH, IW, Cin, OH, OW, Cout,
           //                 KH, KW, stride, dil, ldo, co_off, ldr, act, perm, Mp)
           std::vector<ConvParams> ps;
@@ -61,12 +61,24 @@ PYBIND11_MODULE(_hip, m) {
             p.perm = P<const int>(U(21)); p.Mp = I(22);
             ps.push_back(p);
           }
+          // pool: None, or (in, w1t, b1, w2t, img_bias, B, HW, C, N): pool work items
+          GroupPoolParams gp;
+          if (!pool.is_none()) {
+            auto t = pool.cast<py::tuple>();
+            if (t.size() != 9) throw std::invalid_argument("conv_gemm_grouped: 9-tuple for pool");
+            auto U = [&](int i) { return t[i].cast<uintptr_t>(); };
+            gp.in = P<const bf16>(U(0)); gp.w1t = P<const float>(U(1)); gp.b1 = P<const float>(U(2));
+            gp.w2t = P<const float>(U(3)); gp.img_bias = P<float>(U(4));
+            gp.B = t[5].cast<int>(); gp.HW = t[6].cast<int>(); gp.C = t[7].cast<int>();
+            gp.N = t[8].cast<int>();
+          }
           conv_gemm_grouped(ps.data(), (int)ps.size(), P<const int>(order), nblocks, variant,
-                            S(stream), ks, P<float>(part), P<int>(cnt), cnt_stride);
+                            S(stream), ks, P<float>(part), P<int>(cnt), cnt_stride,
+                            pool.is_none() ? nullptr : &gp);
         },
         py::arg("groups"), py::arg("order"), py::arg("nblocks"), py::arg("variant"),
         py::arg("stream"), py::arg("ks") = 1, py::arg("part") = 0, py::arg("cnt") = 0,
-        py::arg("cnt_stride") = 0);
+        py::arg("cnt_stride") = 0, py::arg("pool") = py::none());
 
   m.def("bias_act", [](uintptr_t in, uintptr_t bias, uintptr_t img_bias, uintptr_t out, long long M,
                        int N, int HW, int act, uintptr_t stream) {

@@ -21,6 +21,7 @@
 // branches on a 33x33 map.
 //
 // Block: 4 waves in a 2x2 arrangement; wave tile = (16*MT pixels) x (16*NT chans).
+#include "aspp_pool.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -37,6 +38,13 @@ struct ConvArgs {
 };
 
 constexpr int kMaxConvGroup = 4;
+constexpr int kPoolGroup = kMaxConvGroup;  // group code of a pool work item; its tile field: the image
+// The image-pooling branch as work items of the grouped launch (aspp_pool.h): in [B][HW][C]
+// -> img_bias [B][N]
+struct PoolArgs {
+  const bf16* in; const float* w1t; const float* b1; const float* w2t; float* img_bias;
+  int B, HW, C, N;
+};
 struct ConvGroupArgs {
   ConvArgs g[kMaxConvGroup];
   const int* order;  // [nblocks] (group << 24) | (K slice << 20) | tile
@@ -45,6 +53,18 @@ struct ConvGroupArgs {
   int* cnt;          // ks > 1, in-launch combine: per-tile tickets [group][cnt_stride], else null
   int cnt_stride;
 };
+struct ConvGroupPoolArgs {
+  ConvGroupArgs ga;
+  PoolArgs pool;
+};
+// Grouped variants (tile parameters) that carry pool work items: those whose fused kernel
+// keeps the plain kernel's VGPR count, occupancy, zero scratch and zero spills (variants 5,
+// 6, 8, 15, 17; kernel-resource-usage remarks of all of them in
+// profiles/aspp_pool_fused_resource_usage.txt). With the extra arm the 32-deep rings (12,
+// 13, 14, 16) allocate one VGPR less and variant 18 three more: those stay unfused, as do
+// the 4-wave tiles (10, 11); none of them is instantiated
+template <int MT, int NT, int ST, int WM, int WN, int BK>
+constexpr bool kGroupPoolOk = WM * WN >= 8 && BK == 64 && NT == 4;
 
 template <int MT, int NT>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
@@ -802,11 +822,61 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_glds_group_kernel(ConvGroup
   }
 }
 
+// The grouped launch with the image-pooling branch as work items of its grid: the same
+// switch with one more arm (the kernel above is left as it is, so a launch without pool
+// items runs the code it always ran). A pool item (K slice field 0: no partials, no
+// ticket) computes image t's pooling branch from the convs' input, complete at launch,
+// into img_bias, which the head reads after this kernel; its LDS is carved from the ring.
+// The arm is reached block-uniformly (e is an SGPR).
 template <int MT, int NT, int ST, int WM = 2, int WN = 2, int BK = 64>
-static void launch_conv_glds_group(const ConvGroupArgs& ga, int nblocks, hipStream_t s) {
+__global__ __launch_bounds__(64 * WM * WN) void conv_glds_group_pool_kernel(ConvGroupPoolArgs gp) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int e = __builtin_amdgcn_readfirstlane(gp.ga.order[blockIdx.x]);
+  const int t = e & 0xfffff, ksl = (e >> 20) & 15;
+  switch (e >> 24) {
+    case 0: glds_tile<MT, NT, ST, WM, WN, BK>(gp.ga.g[0], t, smem, gp.ga.ks, ksl, gp.ga.part, gp.ga.cnt); break;
+    case 1: glds_tile<MT, NT, ST, WM, WN, BK>(gp.ga.g[1], t, smem, gp.ga.ks, ksl, gp.ga.part,
+                                              gp.ga.cnt ? gp.ga.cnt + gp.ga.cnt_stride : nullptr); break;
+    case 2: glds_tile<MT, NT, ST, WM, WN, BK>(gp.ga.g[2], t, smem, gp.ga.ks, ksl, gp.ga.part,
+                                              gp.ga.cnt ? gp.ga.cnt + 2 * gp.ga.cnt_stride : nullptr); break;
+    case 3: glds_tile<MT, NT, ST, WM, WN, BK>(gp.ga.g[3], t, smem, gp.ga.ks, ksl, gp.ga.part,
+                                              gp.ga.cnt ? gp.ga.cnt + 3 * gp.ga.cnt_stride : nullptr); break;
+    case kPoolGroup:
+      if (t < gp.pool.B)
+        aspp_pool_item<64 * WM * WN>(gp.pool.in + (size_t)t * gp.pool.HW * gp.pool.C, gp.pool.w1t,
+                                     gp.pool.b1, gp.pool.w2t, gp.pool.img_bias + (size_t)t * gp.pool.N,
+                                     gp.pool.HW, gp.pool.C, gp.pool.N, smem);
+      break;
+    default: break;
+  }
+}
+
+template <int MT, int NT, int ST, int WM = 2, int WN = 2, int BK = 64>
+static void launch_conv_glds_group(const ConvGroupArgs& ga, int nblocks, hipStream_t s,
+                                   const PoolArgs* pool = nullptr) {
   constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
   const size_t lds = (size_t)ST * (BM + BN) * BK * 2 + 16;
   static_assert((size_t)ST * (BM + BN) * BK * 2 + 16 <= 160 * 1024, "LDS ring too large");
+  if (pool) {
+    if constexpr (kGroupPoolOk<MT, NT, ST, WM, WN, BK>) {
+      if (pool_item_lds(pool->C, pool->N) > lds)
+        throw std::invalid_argument("conv_gemm_grouped: the pool work item does not fit this variant's LDS");
+      static bool pool_attr_set = false;
+      if (!pool_attr_set) {
+        check(hipFuncSetAttribute(
+                  reinterpret_cast<const void*>(&conv_glds_group_pool_kernel<MT, NT, ST, WM, WN, BK>),
+                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+              "conv_glds_group_pool attr");
+        pool_attr_set = true;
+      }
+      hipLaunchKernelGGL((conv_glds_group_pool_kernel<MT, NT, ST, WM, WN, BK>), dim3(nblocks),
+                         dim3(64 * WM * WN), lds, s, ConvGroupPoolArgs{ga, *pool});
+      check_launch("conv_glds_group_pool");
+      return;
+    } else {
+      throw std::invalid_argument("conv_gemm_grouped: this variant carries no pool work items");
+    }
+  }
   static bool attr_set = false;
   if (!attr_set) {
     check(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_glds_group_kernel<MT, NT, ST, WM, WN, BK>),
@@ -974,7 +1044,8 @@ static ConvArgs to_args(const ConvParams& p) {
 }
 
 void conv_gemm_grouped(const ConvParams* ps, int n, const int* order, int nblocks, int variant,
-                       hipStream_t s, int ks, float* part, int* cnt, int cnt_stride) {
+                       hipStream_t s, int ks, float* part, int* cnt, int cnt_stride,
+                       const GroupPoolParams* pool) {
   if (n < 1 || n > kMaxConvGroup) throw std::invalid_argument("conv_gemm_grouped: 1..4 convs");
   if (!order || nblocks < 1) throw std::invalid_argument("conv_gemm_grouped: empty tile order");
   if (ks < 1 || ks > 16 || (ks > 1 && part == nullptr))
@@ -998,24 +1069,34 @@ void conv_gemm_grouped(const ConvParams* ps, int n, const int* order, int nblock
     ga.g[i] = to_args(p);
   }
   ga.order = order;
+  PoolArgs pa{};
+  if (pool) {  // the order table then holds one (kPoolGroup << 24) | b entry per image
+    const GroupPoolParams& q = *pool;
+    if (!q.in || !q.w1t || !q.b1 || !q.w2t || !q.img_bias || q.B < 1 || q.HW < 1)
+      throw std::invalid_argument("conv_gemm_grouped: pool operands missing");
+    if (q.C > kPoolMaxC || q.N > kPoolMaxN || q.C % 8 || q.N % 4 || q.C < 8 || q.N < 4)
+      throw std::invalid_argument("conv_gemm_grouped: pool needs C <= 2048, C % 8, N <= 512, N % 4");
+    pa = PoolArgs{q.in, q.w1t, q.b1, q.w2t, q.img_bias, q.B, q.HW, q.C, q.N};
+  }
+  const PoolArgs* pp = pool ? &pa : nullptr;
   switch (variant) {
-    case 5: launch_conv_glds_group<4, 4, 2, 2, 4>(ga, nblocks, s); break;   // 128 x 256, 8 waves
-    case 6: launch_conv_glds_group<8, 4, 2, 2, 4>(ga, nblocks, s); break;   // 256 x 256, 8 waves
-    case 8: launch_conv_glds_group<4, 4, 3, 2, 4>(ga, nblocks, s); break;   // 128 x 256, 3 stages
-    case 10: launch_conv_glds_group<4, 4, 4, 2, 2>(ga, nblocks, s); break;  // 128 x 128, 4 stages
-    case 11: launch_conv_glds_group<4, 4, 2, 2, 2>(ga, nblocks, s); break;  // 128 x 128, 2 stages
+    case 5: launch_conv_glds_group<4, 4, 2, 2, 4>(ga, nblocks, s, pp); break;   // 128 x 256, 8 waves
+    case 6: launch_conv_glds_group<8, 4, 2, 2, 4>(ga, nblocks, s, pp); break;   // 256 x 256, 8 waves
+    case 8: launch_conv_glds_group<4, 4, 3, 2, 4>(ga, nblocks, s, pp); break;   // 128 x 256, 3 stages
+    case 10: launch_conv_glds_group<4, 4, 4, 2, 2>(ga, nblocks, s, pp); break;  // 128 x 128, 4 stages
+    case 11: launch_conv_glds_group<4, 4, 2, 2, 2>(ga, nblocks, s, pp); break;  // 128 x 128, 2 stages
     // 32-deep stages, 3 in flight
-    case 12: launch_conv_glds_group<8, 4, 4, 2, 4, 32>(ga, nblocks, s); break;  // 256 x 256
-    case 13: launch_conv_glds_group<4, 4, 4, 2, 4, 32>(ga, nblocks, s); break;  // 128 x 256
-    case 14: launch_conv_glds_group<8, 4, 3, 2, 4, 32>(ga, nblocks, s); break;  // 256 x 256, 3 stages
+    case 12: launch_conv_glds_group<8, 4, 4, 2, 4, 32>(ga, nblocks, s, pp); break;  // 256 x 256
+    case 13: launch_conv_glds_group<4, 4, 4, 2, 4, 32>(ga, nblocks, s, pp); break;  // 128 x 256
+    case 14: launch_conv_glds_group<8, 4, 3, 2, 4, 32>(ga, nblocks, s, pp); break;  // 256 x 256, 3 stages
     // 16 waves (4 per SIMD, 64 x 64 per wave): twice the waves of v6 to cover the LDS-DMA
     // and LDS latency of the 1-workgroup-per-CU 256 x 256 tiles (MFMA busy ~23 % in v6)
-    case 15: launch_conv_glds_group<4, 4, 2, 4, 4>(ga, nblocks, s); break;      // 256 x 256
-    case 16: launch_conv_glds_group<4, 4, 4, 4, 4, 32>(ga, nblocks, s); break;  // 256 x 256, 32-deep
+    case 15: launch_conv_glds_group<4, 4, 2, 4, 4>(ga, nblocks, s, pp); break;      // 256 x 256
+    case 16: launch_conv_glds_group<4, 4, 4, 4, 4, 32>(ga, nblocks, s, pp); break;  // 256 x 256, 32-deep
     // 16 waves on half-size tiles (32 x 64 / 64 x 32 per wave): twice the tiles, so the LPT
     // grid's last round (548 tiles of up to 9 taps on 256 CUs at 256 x 256) is finer
-    case 17: launch_conv_glds_group<2, 4, 2, 4, 4>(ga, nblocks, s); break;      // 128 x 256
-    case 18: launch_conv_glds_group<4, 2, 2, 4, 4>(ga, nblocks, s); break;      // 256 x 128
+    case 17: launch_conv_glds_group<2, 4, 2, 4, 4>(ga, nblocks, s, pp); break;      // 128 x 256
+    case 18: launch_conv_glds_group<4, 2, 2, 4, 4>(ga, nblocks, s, pp); break;      // 256 x 128
     default: throw std::invalid_argument("conv_gemm_grouped: variant must be 5, 6, 8, 10-18");
   }
 }

@@ -30,9 +30,17 @@ void conv_gemm(const ConvParams& p, hipStream_t s);
 // (group << 24) | tile picks block i's tile (row-major (m-tile, n-tile) of that
 // conv's GEMM, BM x BN of the variant: 5 128x256, 6 256x256, 8 128x256 3-stage,
 // 10 128x128 4-stage, 11 128x128 2-stage).
+// pool != null: the ASPP image-pooling branch (what aspp_pool computes, bit for bit) runs as
+// extra work items of the same grid, one workgroup per image: order entries (4 << 24) | b.
+struct GroupPoolParams {
+  const bf16* in = nullptr;   // [B, HW, C]: the convs' input
+  const float* w1t = nullptr; const float* b1 = nullptr; const float* w2t = nullptr;
+  float* img_bias = nullptr;  // [B, N]
+  int B = 0, HW = 0, C = 0, N = 0;
+};
 void conv_gemm_grouped(const ConvParams* ps, int n, const int* order, int nblocks, int variant,
                        hipStream_t s, int ks = 1, float* part = nullptr, int* cnt = nullptr,
-                       int cnt_stride = 0);
+                       int cnt_stride = 0, const GroupPoolParams* pool = nullptr);
 
 // Pointwise conv, weight-streamed (pw_conv.hip). w is host-packed per 64-channel
 // chunk: weights in MFMA fragment order [4][ceil(K/32)][64 lanes][8] bf16 followed by

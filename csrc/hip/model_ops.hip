@@ -1,6 +1,7 @@
 // Memory-bound model kernels for gfx950: depthwise conv, fused preprocess+stem,
 // max pool, global average pool, small matvec, fused bilinear upsample + argmax.
 // All NHWC bf16 with 16-byte vector accesses along channels (8 bf16 per lane).
+#include "aspp_pool.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -503,8 +504,7 @@ void maxpool3x3s2(const bf16* in, bf16* out, int B, int IH, int IW, int C, int O
 // 32 slices and four 16-byte loads in flight per lane: with 16 slices and one load per
 // iteration each wave walked 17 pixels through 17 dependent L2/HBM round trips (10 us at
 // B = 32, 8 us at B = 1 where the grid is only 16 workgroups: r8l / r8p step traces).
-constexpr int kGapSlices = 32;
-
+// (kGapSlices and the chain walk: aspp_pool.h)
 __global__ __launch_bounds__(256) void gap_partial_kernel(const bf16* __restrict__ in,
                                                           float* __restrict__ part, int HW, int C) {
   const int b = blockIdx.x, sl = blockIdx.y;
@@ -512,28 +512,13 @@ __global__ __launch_bounds__(256) void gap_partial_kernel(const bf16* __restrict
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int cg = blockIdx.z * 64 + lane;
   __shared__ float red[4][64][8];
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const int p0 = (int)((long long)HW * sl / kGapSlices), p1 = (int)((long long)HW * (sl + 1) / kGapSlices);
-  if (cg < CG) {
-    const bf16* base = in + (long long)b * HW * C + cg * 8;
-    int p = p0 + wid;
-    for (; p + 12 < p1; p += 16) {  // this wave's next 4 pixels: all loads issued first
-      bf16x8 v[4];
+  float acc[1][8] = {{0, 0, 0, 0, 0, 0, 0, 0}};
+  int p0, p1;
+  gap_slice_range(HW, sl, p0, p1);
+  if (cg < CG)  // this wave's chain, 4 pixels per trip: all loads issued first
+    gap_chains<1, 4>(in + (long long)b * HW * C + cg * 8, C, p0 + wid, p1, acc);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = ld8(base + (long long)(p + 4 * u) * C);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += (float)v[u][q];
-    }
-    for (; p < p1; p += 4) {
-      const bf16x8 v = ld8(base + (long long)p * C);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] += (float)v[q];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 8; ++q) red[wid][lane][q] = acc[q];
+  for (int q = 0; q < 8; ++q) red[wid][lane][q] = acc[0][q];
   __syncthreads();
   if (wid == 0 && cg < CG) {
 #pragma unroll
@@ -697,27 +682,7 @@ void matvec(const float* x, const float* w, const float* bias, float* out, int B
 // outputs (one float4 weight load per k) and a K slice; the slices are summed through
 // LDS. A first version gave each thread whole K=320 dot products: ~80 dependent L2
 // round trips per thread, 30 us for one image (profiles/r2_b1 trace).
-constexpr int kPoolMaxC = 2048, kPoolMaxN = 512;
-
-__device__ __forceinline__ float4 pool_slice(const float* __restrict__ wt, const float* s_x, int k0,
-                                             int k1, int N, int q) {
-  float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-  int k = k0;
-  for (; k + 2 <= k1; k += 2) {
-    const float4 w0 = *reinterpret_cast<const float4*>(wt + (size_t)k * N + 4 * q);
-    const float4 w1 = *reinterpret_cast<const float4*>(wt + (size_t)(k + 1) * N + 4 * q);
-    const float x0 = s_x[k], x1 = s_x[k + 1];
-    a0.x += w0.x * x0; a0.y += w0.y * x0; a0.z += w0.z * x0; a0.w += w0.w * x0;
-    a1.x += w1.x * x1; a1.y += w1.y * x1; a1.z += w1.z * x1; a1.w += w1.w * x1;
-  }
-  if (k < k1) {
-    const float4 w0 = *reinterpret_cast<const float4*>(wt + (size_t)k * N + 4 * q);
-    const float x0 = s_x[k];
-    a0.x += w0.x * x0; a0.y += w0.y * x0; a0.z += w0.z * x0; a0.w += w0.w * x0;
-  }
-  return make_float4(a0.x + a1.x, a0.y + a1.y, a0.z + a1.z, a0.w + a1.w);
-}
-
+// (the body, shared with the pool work item of the grouped branch GEMM: aspp_pool.h)
 template <int kPoolThreads>
 __global__ __launch_bounds__(kPoolThreads) void aspp_pool_kernel(const float* __restrict__ part,
                                                                  const float* __restrict__ w1t,
@@ -729,71 +694,13 @@ __global__ __launch_bounds__(kPoolThreads) void aspp_pool_kernel(const float* __
   if (mode & 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   __shared__ float s_pool[kPoolMaxN];
   __shared__ float4 s_red[kPoolThreads];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float inv = 1.f / (float)HW;
-  const float* pb = part + (size_t)b * kGapSlices * C;
-  for (int k = tid; k < C; k += kPoolThreads) {
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < kGapSlices; ++q) s += pb[(size_t)q * C + k];
-    s_gap[k] = s * inv;
-  }
-  const int nq = N >> 2;                    // float4 output columns
-  const int nks = kPoolThreads / nq;        // K slices
-  const int q = tid % nq, ks = tid / nq;
-  __syncthreads();
+  const int b = blockIdx.x;
   // debug (scripts/debug_pool.py): per image [C gap | N pool | 4 x 1024 float4 stage views]
   const size_t dstride = (size_t)C + N + 4 * 4 * kPoolThreads;
   float* dimg = dbg ? dbg + (size_t)b * dstride : nullptr;
   float4* dv = dbg ? reinterpret_cast<float4*>(dimg + C + N) : nullptr;
-  if (dbg)
-    for (int k = tid; k < C; k += kPoolThreads) dimg[k] = s_gap[k];
-  {
-    const int per = (C + nks - 1) / nks;
-    const int k0 = min(C, ks * per), k1 = min(C, k0 + per);
-    if (ks < nks) {
-      const float4 r = pool_slice(w1t, s_gap, k0, k1, N, q);
-      s_red[ks * nq + q] = r;
-      if (dbg) dv[tid] = r;
-    }
-  }
-  __syncthreads();
-  if (tid < nq) {
-    float4 s = s_red[tid];
-    if (dbg) dv[kPoolThreads + tid] = s;
-    for (int j = 1; j < nks; ++j) {
-      const float4 v = s_red[j * nq + tid];
-      if (dbg) dv[kPoolThreads + j * nq + tid] = v;
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    s_pool[4 * tid + 0] = fmaxf(s.x + b1[4 * tid + 0], 0.f);
-    s_pool[4 * tid + 1] = fmaxf(s.y + b1[4 * tid + 1], 0.f);
-    s_pool[4 * tid + 2] = fmaxf(s.z + b1[4 * tid + 2], 0.f);
-    s_pool[4 * tid + 3] = fmaxf(s.w + b1[4 * tid + 3], 0.f);
-  }
-  __syncthreads();
-  if (dbg)
-    for (int k = tid; k < N; k += kPoolThreads) dimg[C + k] = s_pool[k];
-  {
-    const int per = (N + nks - 1) / nks;
-    const int k0 = min(N, ks * per), k1 = min(N, k0 + per);
-    if (ks < nks) {
-      const float4 r = pool_slice(w2t, s_pool, k0, k1, N, q);
-      s_red[ks * nq + q] = r;
-      if (dbg) dv[2 * kPoolThreads + tid] = r;
-    }
-  }
-  __syncthreads();
-  if (tid < nq) {
-    float4 s = s_red[tid];
-    if (dbg) dv[3 * kPoolThreads + tid] = s;
-    for (int j = 1; j < nks; ++j) {
-      const float4 v = s_red[j * nq + tid];
-      if (dbg) dv[3 * kPoolThreads + j * nq + tid] = v;
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-    *reinterpret_cast<float4*>(img_bias + (size_t)b * N + 4 * tid) = s;
-  }
+  aspp_pool_mlp<kPoolThreads>(part + (size_t)b * kGapSlices * C, w1t, b1, w2t, img_bias + (size_t)b * N,
+                              HW, C, N, s_gap, s_pool, s_red, threadIdx.x, kPoolThreads, dimg, dv);
 }
 
 void aspp_pool(const bf16* in, float* ws, const float* w1t, const float* b1, const float* w2t,

@@ -209,10 +209,11 @@ class HipDeepLab(HipPlanModel):
             bops, st = (self._mnv2_block if mnv2 else self._resnet_block)(buf, i, self.blocks[i], B, *st)
             ops += bops
         cat = buf("aspp_cat", B, st[1], st[2], self.cat_c)
-        branches = self._aspp_branches(B, buf, bufs, cat, *st)
-        fork, pool, img_bias = self._aspp_pool(B, buf, bufs, *st)
+        fork, pool, img_bias, item = self._aspp_pool(B, buf, bufs, *st)
         # (SSA_POOL_FORK: the pooling branch forks before the branch GEMMs and joins before the head)
-        ops += fork + branches + pool
+        # (item: the pooling operands where it may run as work items of the grouped branch
+        # GEMM; aspp.branches then covers the pooling steps too, in every variant)
+        ops += fork + self._aspp_branches(B, buf, bufs, cat, *st, pool=pool, item=item)
         head, logits = self._head(B, buf, cat, img_bias, st[1], st[2])
         return ops + head + self._upsample(B, buf, logits, st[1], st[2])
 
@@ -277,9 +278,14 @@ class HipDeepLab(HipPlanModel):
         return [Choice("stem+block0", list(bands.items())[::-1] + tiles +
                        [("separate", [stem] + block0)])], st0
 
-    def _aspp_branches(self, B, buf, bufs, cat, x, h, w, c):
+    def _aspp_branches(self, B, buf, bufs, cat, x, h, w, c, pool=(), item=None):
         """The 1x1 and the atrous branches into their channel slices of ``cat``: one step
-        per branch, or the ``aspp.branches`` choice of grouped launches against them."""
+        per branch, or the ``aspp.branches`` choice of grouped launches against them, then
+        the pooling steps ``pool``. With ``item`` (the pooling operands) the choice covers
+        branches AND pooling: every variant carries the pooling work it implies, so each is
+        timed with it -- the variants of before followed by ``pool``, and after them the
+        ``grouped_v*+pool`` forms whose launch runs the pooling as work items of its grid."""
+        pool = list(pool)
         A = self.aspp_c
         b0w, b0b = self.aspp_b0
         sep = [pw_choice("aspp.b0", lambda *_: K.conv_gemm(
@@ -308,16 +314,28 @@ class HipDeepLab(HipPlanModel):
                         perm=perm)]))
             sep.append(Choice(f"aspp.rate{rate}", variants))
         if len(self.aspp_atrous) <= 3 and c % 8 == 0:
-            return [Choice("aspp.branches",
-                           self._aspp_grouped(B, buf, bufs, cat, x, h, w, c) + [("separate", sep)])]
-        return sep
+            grouped, fused = self._aspp_grouped(B, buf, bufs, cat, x, h, w, c, item)
+            if not fused:
+                return [Choice("aspp.branches", grouped + [("separate", sep)])] + pool
+            return [Choice("aspp.branches", [(n, v + pool) for n, v in grouped] +
+                           [("separate", sep + pool)] + fused)]
+        return sep + pool
 
-    def _aspp_grouped(self, B, buf, bufs, cat, x, h, w, c):
+    def _aspp_grouped(self, B, buf, bufs, cat, x, h, w, c, item=None):
         """All spatial branches (1x1 + atrous) in ONE LPT-ordered LDS-DMA grid
-        (conv_gemm_grouped), per tile shape and split-K factor."""
+        (conv_gemm_grouped), per tile shape and split-K factor. Returns (variants, the same
+        launches with the pooling branch ``item`` as work items of the grid: ``name+pool``)."""
         A, dev = self.aspp_c, self.device
         b0w, b0b = self.aspp_b0
-        grouped = []
+        grouped, fused = [], []
+
+        def add(name, convs, order, gv, **kw):
+            grouped.append((name, [lambda *_: K.conv_gemm_grouped(convs, order, gv, **kw)]))
+            if item is not None and gv in K.GROUP_POOL_VARIANTS and K.pool_item_fits(gv, item["C"], item["N"]):
+                order_p = K.with_pool_items(order, B)  # pool items first: never the tail
+                bufs[f"aspp_order{name[len('grouped_v'):]}p"] = order_p
+                fused.append((name + "+pool", [
+                    lambda *_: K.conv_gemm_grouped(convs, order_p, gv, pool=item, **kw)]))
         # (variant 11, 128x128 tiles / 4 waves / 64 KiB LDS -- the only grouped variant
         # that fits two workgroups per CU -- gave label maps that differed in 26 of 450
         # runs with plan copies on three streams, every other variant 0 / 450:
@@ -335,8 +353,7 @@ class HipDeepLab(HipPlanModel):
                                   perm=K.tap_group_perm(B, h, w, 3, rate, BM, dev)))
             order = K.grouped_tile_order(convs, gv, dev)
             bufs[f"aspp_order{gv}"] = order
-            grouped.append((f"grouped_v{gv}", [
-                lambda *_, convs=convs, order=order, gv=gv: K.conv_gemm_grouped(convs, order, gv)]))
+            add(f"grouped_v{gv}", convs, order, gv)
             # small batches: split-K (a batch-1 grid is ~40 tiles of up to 45 K stages for
             # 256 CUs); fp32 partials + one combine (bias, ReLU) over the concat buffer
             ks_opts = (2, 4, 6) if B <= 2 else (2, 3) if B <= 8 else ()
@@ -352,17 +369,18 @@ class HipDeepLab(HipPlanModel):
                     order_k = K.grouped_tile_order(convs, gv, dev, ks=ks)
                     bufs[f"aspp_order{gv}k{ks}"] = order_k
                     for inl in (False, True):  # in-launch combine by each tile's last K slice
-                        grouped.append((f"grouped_v{gv}k{ks}" + ("c" if inl else ""), [
-                            lambda *_, convs=convs, order=order_k, gv=gv, ks=ks, cnt=(cnt if inl else None):
-                            K.conv_gemm_grouped(convs, order, gv, ks=ks, part=bufs["aspp_part"],
-                                                bias_cat=bufs["const_aspp_bias_cat"], cnt=cnt)]))
-        return grouped
+                        add(f"grouped_v{gv}k{ks}" + ("c" if inl else ""), convs, order_k, gv, ks=ks,
+                            part=bufs["aspp_part"], bias_cat=bufs["const_aspp_bias_cat"],
+                            cnt=cnt if inl else None)
+        return grouped, fused
 
     def _aspp_pool(self, B, buf, bufs, x, h, w, c):
         """The image-pooling branch -> per-image bias of the projection. Returns (ops to run
-        before the branches, ops to run before the head, img_bias)."""
+        before the branches, ops to run before the head, img_bias, the operands for running
+        it as work items of the grouped branch GEMM -- or None where that form is not offered:
+        SSA_POOL_FUSED=0, the side-stream fork, the matvec fall-back shapes)."""
         if not self.has_pool:
-            return [], [], None
+            return [], [], None, None
         A, dev = self.aspp_c, self.device
         img_bias = buf("img_bias", B, A, dtype=torch.float32)
         gws = K.gap_workspace(B, c, dev)
@@ -373,7 +391,7 @@ class HipDeepLab(HipPlanModel):
             return [], [
                 lambda *_: K.global_avgpool(x, gap, B=B, HW=h * w, C=c, ws=gws),
                 lambda *_: K.matvec(gap, self.pool_w, self.pool_b, pooled, B=B, N=A, K=c, act="relu"),
-                lambda *_: K.matvec(pooled, self.proj_pool_w, None, img_bias, B=B, N=A, K=A)], img_bias
+                lambda *_: K.matvec(pooled, self.proj_pool_w, None, img_bias, B=B, N=A, K=A)], img_bias, None
         # GAP partials + one per-image kernel for the pooled MLP (aspp_pool)
         w1t = self.pool_w.t().contiguous()
         w2t = self.proj_pool_w.t().contiguous()
@@ -381,7 +399,8 @@ class HipDeepLab(HipPlanModel):
         pool_op = (lambda *_: K.aspp_pool(
             x, gws, w1t, self.pool_b, w2t, img_bias, B=B, HW=h * w, C=c, N=A))
         if not (os.environ.get("SSA_POOL_FORK", "0") == "1" and torch.cuda.is_available()):
-            return [], [pool_op], img_bias
+            item = dict(x=x, w1t=w1t, b1=self.pool_b, w2t=w2t, img_bias=img_bias, B=B, HW=h * w, C=c, N=A)
+            return [], [pool_op], img_bias, item if os.environ.get("SSA_POOL_FUSED", "1") != "0" else None
         # the pooling branch (GAP partials + per-image MLP: 32 + 32 small
         # workgroups, ~26 us of latency at B = 32) on a side stream forked before
         # the grouped branch GEMM and joined before the head: its few waves fit
@@ -398,7 +417,7 @@ class HipDeepLab(HipPlanModel):
                 pool_op(*args)
             ev_j.record(side)
 
-        return [fork_op], [lambda *_: torch.cuda.current_stream().wait_event(ev_j)], img_bias
+        return [fork_op], [lambda *_: torch.cuda.current_stream().wait_event(ev_j)], img_bias, None
 
     def _head(self, B, buf, cat, img_bias, h, w):
         """Projection and logits: two steps, or the ``aspp.head`` choice of the fused kernel

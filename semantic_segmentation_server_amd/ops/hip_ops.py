@@ -134,6 +134,16 @@ def tap_group_perm(B: int, H: int, W: int, k: int, dil: int, BM: int, device=Non
 GROUP_TILE = {5: (128, 256), 6: (256, 256), 8: (128, 256), 10: (128, 128), 11: (128, 128),
               12: (256, 256), 13: (128, 256), 14: (256, 256), 15: (256, 256), 16: (256, 256),
               17: (128, 256), 18: (256, 128)}
+# the image-pooling branch as work items of the grouped launch: order entries
+# (POOL_GROUP << 24) | image, carried by these variants (with the extra arm their kernels keep
+# VGPRs, occupancy and zero scratch / spills, conv_gemm.hip kGroupPoolOk; img_bias and the
+# concat buffer are bit-identical to the separate kernels', tests/test_aspp_pool_fused_gpu.py)
+POOL_GROUP = 4
+GROUP_POOL_VARIANTS = (5, 6, 8, 15, 17)
+# dynamic LDS of a grouped launch (stages x (BM + BN) rows x stage row bytes + tap list): a
+# pool item carves (33 C + N) floats + 16 KiB from it
+GROUP_LDS = {5: 98320, 6: 131088, 8: 147472, 10: 131088, 11: 65552, 12: 131088, 13: 98320,
+             14: 98320, 15: 131088, 16: 131088, 17: 98320, 18: 98320}
 
 
 def _tile_taps(B: int, H: int, W: int, k: int, dil: int, BM: int,
@@ -160,10 +170,15 @@ def _tile_taps(B: int, H: int, W: int, k: int, dil: int, BM: int,
     return sum(((tile >> t) & 1) for t in range(k * k))
 
 
-def grouped_tile_order(convs: List[dict], variant: int, device=None, xcds: int = 1, ks: int = 1) -> torch.Tensor:
+def grouped_tile_order(convs: List[dict], variant: int, device=None, xcds: int = 1, ks: int = 1,
+                       pool: int = 0) -> torch.Tensor:
     """Block -> tile table of ``conv_gemm_grouped``: every tile of every conv as
     (group << 24) | tile, heaviest first (work = live taps x 64-channel K chunks;
     longest-processing-time order, so the short 1x1 / edge tiles fill the tail).
+
+    ``pool`` > 0: one pool work item per image, (POOL_GROUP << 24) | b for b < pool, FIRST in
+    the table (a latency chain shorter than a heavy tile: it must start with the first round,
+    not form the tail); the GEMM entries and their order are those of ``pool`` = 0.
 
     ``xcds > 1`` (8 on MI355X): block i runs on XCD i % xcds, so each XCD gets one
     contiguous run of every conv's row tiles (LPT order inside it) -- a dilated
@@ -185,7 +200,7 @@ def grouped_tile_order(convs: List[dict], variant: int, device=None, xcds: int =
                     part.append(min(xcds - 1, tm * xcds // max(1, ntm)))
     if xcds <= 1:
         idx = sorted(range(len(ent)), key=lambda i: (-cost[i], i))
-        return torch.tensor([ent[i] for i in idx], dtype=torch.int32).to(device).contiguous()
+        return with_pool_items(torch.tensor([ent[i] for i in idx], dtype=torch.int32), pool).to(device).contiguous()
     lists = [sorted((i for i in range(len(ent)) if part[i] == x), key=lambda i: (-cost[i], i))
              for x in range(xcds)]
     out, j = [], 0
@@ -199,7 +214,22 @@ def grouped_tile_order(convs: List[dict], variant: int, device=None, xcds: int =
                     out.append(ent[lists[donor].pop()])
         j += 1
     assert sorted(out) == sorted(ent)
-    return torch.tensor(out, dtype=torch.int32).to(device).contiguous()
+    return with_pool_items(torch.tensor(out, dtype=torch.int32), pool).to(device).contiguous()
+
+
+def pool_item_fits(variant: int, C: int, N: int) -> bool:
+    """Whether a pool work item's LDS ([32][C] slice partials, gap[C], pooled[N], 1024 float4)
+    fits the grouped launch's ring (MobileNetV2's C = 320 does, ResNet's C = 2048 does not)."""
+    return (33 * C + N) * 4 + 16384 <= GROUP_LDS[variant]
+
+
+def with_pool_items(order: torch.Tensor, images: int) -> torch.Tensor:
+    """``order`` with one pool work item per image, (POOL_GROUP << 24) | b, in front of it."""
+    if images <= 0:
+        return order
+    head = torch.tensor([(POOL_GROUP << 24) | b for b in range(images)], dtype=torch.int32,
+                        device=order.device)
+    return torch.cat([head, order]).contiguous()
 
 
 def grouped_tile_order_branch(convs: List[dict], variant: int, device=None, xcds: int = 8) -> torch.Tensor:
@@ -275,7 +305,7 @@ def _branch_affine(tiles, heavy, xcds, device):
 
 def conv_gemm_grouped(convs: List[dict], order: torch.Tensor, variant: int = 5, ks: int = 1,
                       part: Optional[torch.Tensor] = None, bias_cat: Optional[torch.Tensor] = None,
-                      cnt: Optional[torch.Tensor] = None) -> None:
+                      cnt: Optional[torch.Tensor] = None, pool: Optional[dict] = None) -> None:
     """Up to 4 independent stride-1 'same' NHWC convs with one Cout (the ASPP branches)
     in ONE LDS-DMA grid, tiles in the ``grouped_tile_order`` table. Each conv is a
     dict of conv_gemm's arguments: x, w, bias, out, B, IH, IW, Cin, OH, OW, Cout, k,
@@ -287,7 +317,12 @@ def conv_gemm_grouped(convs: List[dict], order: torch.Tensor, variant: int = 5, 
     the shared activation into ``out``: the convs must tile [0, ldo) of one output. With
     ``cnt`` (int32, >= 4 x the largest conv's tile count, zeroed once: the last arriver of
     each tile resets its word) the tile's last arriving K slice does that sum inside the
-    launch (no combine kernel; ``bias_cat`` is then unused)."""
+    launch (no combine kernel; ``bias_cat`` is then unused).
+
+    ``pool`` (a dict of aspp_pool's operands without ws: x, w1t, b1, w2t, img_bias, B, HW,
+    C, N; variants in GROUP_POOL_VARIANTS): the image-pooling branch runs as one extra
+    workgroup per image of the same grid (``grouped_tile_order(..., pool=B)``) and writes
+    img_bias, bit-identical to ``aspp_pool``; nothing in the launch reads img_bias."""
     if not 1 <= len(convs) <= 4:
         raise ValueError("conv_gemm_grouped: 1..4 convs")
     if variant not in GROUP_TILE:
@@ -324,15 +359,36 @@ def conv_gemm_grouped(convs: List[dict], order: torch.Tensor, variant: int = 5, 
                        Cin, OH, OW, Cout, k, k, 1, dil, ldo, co_off, Cout, ACT[c.get("act")],
                        _ptr(perm), Mp))
     _chk(order, torch.int32, "order")
-    if not getattr(order, "_ssa_checked", False):  # every block maps to a real tile
+    npool, pool_t = 0, None
+    if pool is not None:
+        if variant not in GROUP_POOL_VARIANTS:
+            raise ValueError(f"conv_gemm_grouped: pool items need a variant in {GROUP_POOL_VARIANTS}")
+        npool, pHW, pC, pN = (pool[n] for n in ("B", "HW", "C", "N"))
+        if pC > 2048 or pN > 512 or pC % 8 or pN % 4 or npool < 1 or pHW < 1:
+            raise ValueError("conv_gemm_grouped: pool needs C <= 2048, C % 8, N <= 512, N % 4")
+        if not pool_item_fits(variant, pC, pN):
+            raise ValueError("conv_gemm_grouped: the pool work item does not fit this variant's LDS")
+        _chk(pool["x"], torch.bfloat16, "pool x", npool * pHW * pC)
+        _chk(pool["w1t"], torch.float32, "pool w1t", pC * pN)
+        _chk(pool["b1"], torch.float32, "pool b1", pN)
+        _chk(pool["w2t"], torch.float32, "pool w2t", pN * pN)
+        _chk(pool["img_bias"], torch.float32, "pool img_bias", npool * pN)
+        pool_t = (_ptr(pool["x"]), _ptr(pool["w1t"]), _ptr(pool["b1"]), _ptr(pool["w2t"]),
+                  _ptr(pool["img_bias"]), npool, pHW, pC, pN)
+    if not getattr(order, "_ssa_checked", None) == npool:  # every block maps to a real tile
         oc = order.cpu().long()
+        isp = (oc >> 24) == POOL_GROUP
+        if sorted(oc[isp].tolist()) != [(POOL_GROUP << 24) | b for b in range(npool)]:
+            raise ValueError("conv_gemm_grouped: the order table must hold one pool item per image "
+                             "(and none without pool operands)")
+        oc = oc[~isp]
         g, t, sl = oc >> 24, oc & 0xFFFFF, (oc >> 20) & 15
         lim = torch.tensor(tiles)[g.clamp(0, len(tiles) - 1)]
         if (g < 0).any() or (g >= len(convs)).any() or (t >= lim).any() or (sl >= ks).any():
             raise ValueError("conv_gemm_grouped: order entry out of range")
         if oc.numel() != sum(tiles) * ks:
             raise ValueError("conv_gemm_grouped: the order table must list every tile's K slices once")
-        order._ssa_checked = True
+        order._ssa_checked = npool
     if ks > 1:
         c0 = convs[0]
         ldo, Mo = c0.get("ldo", c0["Cout"]), c0["B"] * c0["OH"] * c0["OW"]
@@ -350,7 +406,7 @@ def conv_gemm_grouped(convs: List[dict], order: torch.Tensor, variant: int = 5, 
             _chk(cnt, torch.int32, "cnt", 4 * max(tiles))
     _hip_mod().conv_gemm_grouped(groups, _ptr(order), order.numel(), variant, _stream(), int(ks),
                                  _ptr(part) if ks > 1 else 0, _ptr(cnt) if (ks > 1 and cnt is not None) else 0,
-                                 max(tiles))
+                                 max(tiles), pool_t)
     _dbg('conv_gemm_grouped')
     if ks > 1 and cnt is None:
         _hip_mod().stream_combine(_ptr(part), _ptr(bias_cat), 0, _ptr(c0["out"]), int(ks), Mo, ldo, _stream(),
