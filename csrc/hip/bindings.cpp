@@ -450,6 +450,25 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.attr("MASK_RLE_CHUNK") = mask_rle_chunk();
 
+  m.def("class_regions_workspace_bytes", &class_regions_workspace_bytes);
+  m.def("class_regions",
+        [](uintptr_t labels, int B, int H, int W, int crop_h, int crop_w, uint64_t c0, uint64_t c1,
+           uint64_t c2, uint64_t c3, int min_pixels, int K, uintptr_t out, uintptr_t ws,
+           uintptr_t stream) {
+          ClassRegionsParams p;
+          p.labels = P<const uint8_t>(labels); p.B = B; p.H = H; p.W = W;
+          p.crop_h = crop_h; p.crop_w = crop_w; p.min_pixels = min_pixels; p.K = K;
+          const uint64_t c[4] = {c0, c1, c2, c3};  // the 256-bit class set, 64 bits a word
+          for (int i = 0; i < 8; ++i) p.classes[i] = (uint32_t)(c[i >> 1] >> (32 * (i & 1)));
+          p.out = P<uint32_t>(out); p.ws = P<uint32_t>(ws);
+          class_regions(p, S(stream));
+        },
+        py::arg("labels"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("crop_h"),
+        py::arg("crop_w"), py::arg("c0"), py::arg("c1"), py::arg("c2"), py::arg("c3"),
+        py::arg("min_pixels"), py::arg("K"), py::arg("out"), py::arg("ws"), py::arg("stream"));
+  m.attr("REGION_TILE") = class_regions_tile();
+  m.attr("REGION_CANDIDATES") = class_regions_candidates();
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

@@ -1,0 +1,492 @@
+// Class regions of the label maps (the v2 GetClassRegions RPC).
+//
+// A region is a maximal 8-connected set of pixels of ONE class inside the letterbox-valid
+// crop labels[:crop_h, :crop_w], for the classes of a 256-bit served set; pixels of other
+// classes belong to no region and connect nothing. With the flat crop index i = y * crop_w
+// + x, a region's root is its smallest i. Regions of at least min_pixels pixels pass and are
+// ordered by (pixels descending, root ascending). Per frame the output is uint32[4 + 6 K]:
+//   word 0  n_regions (the true number that pass; may exceed K)   word 2  crop_w
+//   word 1  N = crop_w * crop_h                                   word 3  crop_h
+//   then, for the first min(n_regions, K) regions in that order, six words:
+//     (label << 24) | root, pixels, sum_x, sum_y, x_min | y_min << 16, x_max | y_max << 16
+// Words past those are not written. postprocess/regions.py is the numpy definition.
+//
+// A fixed sequence of seven launches, no host round trip, no allocation (capturable). The
+// workspace holds per frame parent[N], cnt[N], kBuckets x 6 x kMaxK statistics words, a
+// candidate counter and 2 x kCandidates candidate words; every word that is read is written by an
+// earlier kernel of the SAME run.
+//   k_cr_local   one workgroup per kTile x kTile tile: union-find in LDS (atomicMin linking:
+//                every root is the minimum index of its set). A pixel starts at the first
+//                pixel of its horizontal same-class run (one ballot per row), so only runs
+//                of adjacent rows are united, once per touching pair. Flattened: parent[i]
+//                = flat index of i's tile-local root (kNone outside the class set), cnt[i]
+//                = size of the tile-local component at its root, 0 elsewhere.
+//   k_cr_merge   the pixels of every tile's top row and left column are united with their
+//                same-class neighbours in the adjacent tiles (the diagonal ones across a
+//                tile corner included): lock-free find (path halving) + atomicMin as the
+//                global union-find of postprocess.hip, parents read and written with
+//                agent-scope atomics. No workgroup waits on another. The final root of a
+//                component is its smallest flat index whatever the arrival order.
+//   k_cr_count   every tile-local root that is not the final root moves its count to the
+//                final root, one integer atomic per (tile, component), and points at it.
+//   k_cr_gather  the roots with cnt >= min_pixels are appended to the frame's candidate list
+//                (at most kCandidates, guaranteed by N / min_pixels <= kCandidates).
+//   k_cr_select  one workgroup per frame: the candidates, keyed (pixels, ~root), are ordered
+//                by a bitonic sort in LDS (the keys are distinct, so the order does not
+//                depend on how the list was filled). Header and words 0, 1 of the first K
+//                records are written, the K statistics slots are reset, and cnt[root]
+//                becomes kSlotBit | rank for those K roots.
+//   k_cr_stats   per tile: coordinate sums and the bounding box of the pixels whose root
+//                holds a slot, privatised in LDS per tile-local key (one set of LDS atomics
+//                per horizontal run of a key, in closed form), then one set of global
+//                integer atomics per (tile, component). A slot has kBuckets copies and a tile adds to
+//                the copy of its index modulo kBuckets: a region that covers the frame would
+//                otherwise send every tile's atomics to one address, where they queue.
+//   k_cr_emit    folds a slot's copies and packs them into words 2 .. 5 of the records.
+// All sums are integer: the result is exact and independent of any arrival order.
+#include "kernels.h"
+
+namespace ssa {
+namespace {
+
+constexpr int kTile = 32;
+constexpr int kTilePix = kTile * kTile;
+constexpr int kThreads = 256;
+constexpr int kPixPerThread = kTilePix / kThreads;
+constexpr int kCandidates = 4096;
+constexpr int kMaxK = 256;
+constexpr int kStatWords = 6;  // sum_x, sum_y, x_min, y_min, x_max, y_max
+constexpr int kBuckets = 16;   // copies of a statistics slot
+constexpr int kSelThreads = 1024;
+constexpr uint32_t kNone = 0xFFFFFFFFu;
+constexpr uint32_t kSlotBit = 0x80000000u;
+
+struct CrArgs {
+  const uint8_t* labels;
+  uint32_t* out;
+  uint32_t* ws;
+  uint32_t cls[8];
+  int H, W, crop_h, crop_w, K, N;
+  uint32_t min_pixels;
+};
+
+constexpr size_t kTailWords = (size_t)kStatWords * kMaxK * kBuckets + 2 + 2 * (size_t)kCandidates;
+__host__ __device__ __forceinline__ size_t frame_words(size_t N) { return 2 * N + kTailWords; }
+__device__ __forceinline__ size_t frame_words(const CrArgs& a) { return frame_words((size_t)a.N); }
+__device__ __forceinline__ uint32_t* parent_of(const CrArgs& a, int b) { return a.ws + b * frame_words(a); }
+__device__ __forceinline__ uint32_t* cnt_of(const CrArgs& a, int b) { return parent_of(a, b) + a.N; }
+__device__ __forceinline__ uint32_t* stats_of(const CrArgs& a, int b) { return parent_of(a, b) + 2 * (size_t)a.N; }
+// [0]: number of candidates, [2 + 2 j], [3 + 2 j]: pixels and root of candidate j
+__device__ __forceinline__ uint32_t* cand_of(const CrArgs& a, int b) {
+  return stats_of(a, b) + kStatWords * kMaxK * kBuckets;
+}
+
+__device__ __forceinline__ bool served(const CrArgs& a, int l) { return (a.cls[l >> 5] >> (l & 31)) & 1u; }
+
+// ---- union-find in LDS (one tile) -------------------------------------------------------
+__device__ __forceinline__ uint32_t lds_ld(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ uint32_t lfind(uint32_t* l, uint32_t x) {
+  uint32_t y = lds_ld(l + x);
+  while (y != x) {
+    x = y;
+    y = lds_ld(l + x);
+  }
+  return x;
+}
+
+__device__ void lunite(uint32_t* l, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = lfind(l, a);
+    b = lfind(l, b);
+    if (a == b) return;
+    if (a < b) {
+      const uint32_t old = atomicMin(l + b, a);
+      if (old == b) return;
+      b = old;
+    } else {
+      const uint32_t old = atomicMin(l + a, b);
+      if (old == a) return;
+      a = old;
+    }
+  }
+}
+
+// ---- union-find in global memory (across tiles, inside one launch) ------------------------
+__device__ __forceinline__ uint32_t ld_agent(const uint32_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ uint32_t gfind(uint32_t* L, uint32_t x) {  // with path halving
+  uint32_t y = ld_agent(L + x);
+  while (y != x) {
+    const uint32_t z = ld_agent(L + y);
+    if (z != y) __hip_atomic_store(L + x, z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = y;
+    y = z;
+  }
+  return x;
+}
+
+__device__ void gunite(uint32_t* L, uint32_t a, uint32_t b) {
+  for (;;) {
+    a = gfind(L, a);
+    b = gfind(L, b);
+    if (a == b) return;
+    if (a < b) {
+      const uint32_t old = atomicMin(L + b, a);
+      if (old == b) return;
+      b = old;
+    } else {
+      const uint32_t old = atomicMin(L + a, b);
+      if (old == a) return;
+      a = old;
+    }
+  }
+}
+
+// Root of x once no kernel changes the parents any more (plain loads).
+__device__ __forceinline__ uint32_t find_plain(const uint32_t* L, uint32_t x) {
+  uint32_t y = L[x];
+  while (y != x) {
+    x = y;
+    y = L[x];
+  }
+  return x;
+}
+
+// Length of the run that starts at column lx of a tile row, from the row's 32 start flags.
+__device__ __forceinline__ uint32_t run_length(uint32_t row_starts, int lx) {
+  const uint32_t after = lx == kTile - 1 ? 0u : row_starts >> (lx + 1);
+  return after ? (uint32_t)__ffs((int)after) : (uint32_t)(kTile - lx);
+}
+
+// ---- 1. tile-local components --------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_cr_local(CrArgs a) {
+  __shared__ short lab[kTilePix];      // class id, -1: outside the crop or the class set
+  __shared__ uint32_t par[kTilePix];
+  __shared__ uint32_t size[kTilePix];
+  const int b = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const uint8_t* img = a.labels + (size_t)b * a.H * a.W;
+  const int tid = threadIdx.x;
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) cand_of(a, b)[0] = 0;
+  // a wave holds two tile rows (lane & 31 = column): a pixel's first parent is the start of
+  // its horizontal run, from the row's ballot of "differs from the pixel to its left"
+  uint32_t start[kPixPerThread], len[kPixPerThread];  // len: of the run, at its start
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads, lx = i & (kTile - 1), x = x0 + lx, y = y0 + i / kTile;
+    int l = -1;
+    if (x < a.crop_w && y < a.crop_h) {
+      l = img[(size_t)y * a.W + x];
+      if (!served(a, l)) l = -1;
+    }
+    const int left = __shfl_up(l, 1, 64);
+    const unsigned long long starts = __ballot(lx == 0 || left != l);
+    const uint32_t row = (uint32_t)(starts >> (tid & 32));  // bit 0 is always set
+    start[k] = (uint32_t)(i - lx + 31 - __clz((int)(row & ((2u << lx) - 1u))));
+    len[k] = run_length(row, lx);
+    lab[i] = (short)l;
+    par[i] = start[k];
+    size[i] = 0;
+  }
+  __syncthreads();
+  // a run is united with each same-class run of the row above that it touches (8-neighbours),
+  // by the first of its pixels that touches it
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads, lx = i & (kTile - 1);
+    const int l = lab[i];
+    if (l < 0 || i < kTile) continue;
+    const bool left = lx > 0 && lab[i - 1] == l, right = lx < kTile - 1 && lab[i + 1] == l;
+    const bool upleft = lx > 0 && lab[i - kTile - 1] == l, upright = lx < kTile - 1 && lab[i - kTile + 1] == l;
+    if (lab[i - kTile] == l) {
+      if (!(left && upleft)) lunite(par, i, i - kTile);  // else the pixel to the left did it
+    } else {
+      if (upleft && !left) lunite(par, i, i - kTile - 1);
+      if (upright && !right) lunite(par, i, i - kTile + 1);  // else the pixel to the right does
+    }
+  }
+  __syncthreads();
+  // flatten: the run starts find their roots, then every pixel takes its start's
+  uint32_t root[kPixPerThread];
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads;
+    root[k] = (lab[i] >= 0 && start[k] == (uint32_t)i) ? lfind(par, i) : kNone;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k)
+    if (root[k] != kNone) par[tid + k * kThreads] = root[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads;
+    const bool on = lab[i] >= 0;
+    const uint32_t r = on ? par[start[k]] : kNone;
+    root[k] = r;
+    if (on && start[k] == (uint32_t)i) atomicAdd(&size[r], len[k]);  // one add per run
+  }
+  __syncthreads();
+  uint32_t* parent = parent_of(a, b);
+  uint32_t* cnt = cnt_of(a, b);
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads, x = x0 + (i & (kTile - 1)), y = y0 + i / kTile;
+    if (x >= a.crop_w || y >= a.crop_h) continue;
+    const uint32_t r = root[k];
+    const int g = y * a.crop_w + x;
+    parent[g] = r == kNone ? kNone
+                           : (uint32_t)((y0 + (int)(r / kTile)) * a.crop_w + x0 + (int)(r & (kTile - 1)));
+    cnt[g] = r == (uint32_t)i ? size[i] : 0u;
+  }
+}
+
+// ---- 2. unions across tile edges -----------------------------------------------------------
+// One wave per tile: lanes 0 .. 31 take the tile's top row (neighbours N, NW, NE in the row
+// above), lanes 32 .. 63 its left column (neighbours W, NW, SW in the column to the left).
+// Every pair of 8-neighbours in different tiles is seen from at least one side.
+__global__ __launch_bounds__(64) void k_cr_merge(CrArgs a) {
+  const int b = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const uint8_t* img = a.labels + (size_t)b * a.H * a.W;
+  uint32_t* parent = parent_of(a, b);
+  const int t = threadIdx.x & 31;
+  const bool top = threadIdx.x < 32;
+  const int x = top ? x0 + t : x0, y = top ? y0 : y0 + t;
+  if (x >= a.crop_w || y >= a.crop_h) return;
+  if (top ? y == 0 : x == 0) return;
+  const int l = img[(size_t)y * a.W + x];
+  if (!served(a, l)) return;
+  const uint32_t g = (uint32_t)(y * a.crop_w + x);
+#pragma unroll
+  for (int d = -1; d <= 1; ++d) {
+    const int nx = top ? x + d : x - 1, ny = top ? y - 1 : y + d;
+    if (nx < 0 || nx >= a.crop_w || ny < 0 || ny >= a.crop_h) continue;
+    if (img[(size_t)ny * a.W + nx] == l) gunite(parent, g, (uint32_t)(ny * a.crop_w + nx));
+  }
+}
+
+// ---- 3. component sizes at the final roots -------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_cr_count(CrArgs a) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= a.N) return;
+  uint32_t* parent = parent_of(a, b);
+  uint32_t* cnt = cnt_of(a, b);
+  const uint32_t c = cnt[i];  // non-zero at tile-local roots only; only final roots are added to
+  if (c == 0) return;
+  // other threads of this launch walk through i: they meet its old parent or the root
+  const uint32_t r = gfind(parent, (uint32_t)i);
+  if (r == (uint32_t)i) return;
+  __hip_atomic_store(parent + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  atomicAdd(cnt + r, c);
+  cnt[i] = 0;
+}
+
+// ---- 4. candidates ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kThreads) void k_cr_gather(CrArgs a) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= a.N) return;
+  const uint32_t c = cnt_of(a, b)[i];
+  if (c < a.min_pixels) return;
+  uint32_t* cand = cand_of(a, b);
+  const uint32_t at = atomicAdd(cand, 1u);
+  if (at < (uint32_t)kCandidates) {
+    cand[2 + 2 * at] = c;
+    cand[3 + 2 * at] = (uint32_t)i;
+  }
+}
+
+// ---- 5. select and order -------------------------------------------------------------------
+__global__ __launch_bounds__(kSelThreads) void k_cr_select(CrArgs a) {
+  __shared__ unsigned long long key[kCandidates];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  uint32_t* cnt = cnt_of(a, b);
+  const uint32_t* cand = cand_of(a, b);
+  const uint32_t n_true = cand[0];
+  const int n = (int)(n_true < (uint32_t)kCandidates ? n_true : (uint32_t)kCandidates);
+  int n2 = 2;
+  while (n2 < n) n2 <<= 1;
+  for (int i = tid; i < n2; i += kSelThreads)  // padding sorts last: pixels >= 1
+    key[i] = i < n ? ((unsigned long long)cand[2 + 2 * i] << 32) | (uint32_t)~cand[3 + 2 * i] : 0ull;
+  __syncthreads();
+  // bitonic sort, descending: keys are distinct (one root each), so the order is unique
+  for (int size = 2; size <= n2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < n2; i += kSelThreads) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const unsigned long long ki = key[i], kj = key[j];
+          const bool desc = (i & size) == 0;
+          if (desc ? ki < kj : ki > kj) {
+            key[i] = kj;
+            key[j] = ki;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  uint32_t* o = a.out + (size_t)b * (4 + 6 * a.K);
+  uint32_t* st = stats_of(a, b);
+  const uint8_t* img = a.labels + (size_t)b * a.H * a.W;
+  const int kept = n < a.K ? n : a.K;
+  for (int i = tid; i < kept; i += kSelThreads) {
+    const unsigned long long k = key[i];
+    const uint32_t root = ~(uint32_t)k, pixels = (uint32_t)(k >> 32);
+    const int y = (int)(root / (uint32_t)a.crop_w), x = (int)(root - (uint32_t)y * a.crop_w);
+    o[4 + 6 * i] = ((uint32_t)img[(size_t)y * a.W + x] << 24) | root;
+    o[4 + 6 * i + 1] = pixels;
+    cnt[root] = kSlotBit | (uint32_t)i;
+  }
+  for (int j = tid; j < kept * kBuckets; j += kSelThreads) {  // slot j / kBuckets, copy j % kBuckets
+    uint32_t* s = st + kStatWords * j;
+    s[0] = 0; s[1] = 0; s[2] = kNone; s[3] = kNone; s[4] = 0; s[5] = 0;
+  }
+  if (tid == 0) {
+    o[0] = n_true;
+    o[1] = (uint32_t)a.N;
+    o[2] = (uint32_t)a.crop_w;
+    o[3] = (uint32_t)a.crop_h;
+  }
+}
+
+// ---- 6. coordinate sums and bounding boxes of the kept regions ---------------------------------
+__global__ __launch_bounds__(kThreads) void k_cr_stats(CrArgs a) {
+  __shared__ uint32_t slot[kTilePix];  // per tile-local key: 0 unused, 1 used, then slot + 2 or 1
+  __shared__ uint32_t acc[kStatWords][kTilePix];
+  const int b = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
+  const uint32_t* parent = parent_of(a, b);
+  const uint32_t* cnt = cnt_of(a, b);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads;
+    slot[i] = 0;
+    acc[0][i] = 0; acc[1][i] = 0; acc[2][i] = kNone; acc[3][i] = kNone; acc[4][i] = 0; acc[5][i] = 0;
+  }
+  __syncthreads();
+  // key of a pixel: its parent if that lies in this tile (its tile-local root, or for such a
+  // root a smaller root of the same region), else the pixel itself. Every pixel of one key is
+  // in one region, and a key is always a pixel of this tile.
+  int key[kPixPerThread];
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads, x = x0 + (i & (kTile - 1)), y = y0 + i / kTile;
+    key[k] = -1;
+    if (x >= a.crop_w || y >= a.crop_h) continue;
+    const uint32_t p = parent[y * a.crop_w + x];
+    if (p == kNone) continue;
+    const int py = (int)(p / (uint32_t)a.crop_w), px = (int)(p - (uint32_t)py * a.crop_w);
+    const int ty = py - y0, tx = px - x0;
+    key[k] = (tx >= 0 && tx < kTile && ty >= 0 && ty < kTile) ? ty * kTile + tx : i;
+    slot[key[k]] = 1;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads;
+    if (slot[i] == 0) continue;
+    const int x = x0 + (i & (kTile - 1)), y = y0 + i / kTile;
+    const uint32_t c = cnt[find_plain(parent, (uint32_t)(y * a.crop_w + x))];
+    slot[i] = (c & kSlotBit) ? (c & ~kSlotBit) + 2 : 1;
+  }
+  __syncthreads();
+  // a wave holds two tile rows: the first pixel of every horizontal run of one key adds the
+  // whole run in closed form
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads, lx = i & (kTile - 1);
+    const uint32_t x = (uint32_t)(x0 + lx), y = (uint32_t)(y0 + i / kTile);
+    const int kk = key[k];
+    const int prev = __shfl_up(kk, 1, 64);  // by every lane, before any branch
+    const bool head = lx == 0 || prev != kk;
+    const unsigned long long heads = __ballot(head);
+    if (!head || kk < 0 || slot[kk] < 2) continue;
+    const uint32_t n = run_length((uint32_t)(heads >> (tid & 32)), lx);
+    atomicAdd(&acc[0][kk], n * (2 * x + n - 1) / 2); atomicAdd(&acc[1][kk], n * y);
+    atomicMin(&acc[2][kk], x); atomicMin(&acc[3][kk], y);
+    atomicMax(&acc[4][kk], x + n - 1); atomicMax(&acc[5][kk], y);
+  }
+  __syncthreads();
+  uint32_t* st = stats_of(a, b) + kStatWords * ((blockIdx.y * gridDim.x + blockIdx.x) % kBuckets);
+#pragma unroll
+  for (int k = 0; k < kPixPerThread; ++k) {
+    const int i = tid + k * kThreads;
+    if (slot[i] < 2) continue;
+    uint32_t* s = st + kStatWords * kBuckets * (slot[i] - 2);
+    // scattered global atomics are the cost of this kernel. Both sums go in one 64-bit add
+    // (8-byte aligned; sum_x < 2^32 by the geometry check, so nothing carries into sum_y).
+    // A box edge that does not improve on the value read is not sent: the stored edges only
+    // tighten during the launch, so a stale read can cost a needless atomic, never skip one.
+    atomicAdd(reinterpret_cast<unsigned long long*>(s), ((unsigned long long)acc[1][i] << 32) | acc[0][i]);
+    if (acc[2][i] < s[2]) atomicMin(s + 2, acc[2][i]);
+    if (acc[3][i] < s[3]) atomicMin(s + 3, acc[3][i]);
+    if (acc[4][i] > s[4]) atomicMax(s + 4, acc[4][i]);
+    if (acc[5][i] > s[5]) atomicMax(s + 5, acc[5][i]);
+  }
+}
+
+// ---- 7. pack ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMaxK) void k_cr_emit(CrArgs a) {
+  const int b = blockIdx.x, i = threadIdx.x;
+  uint32_t* o = a.out + (size_t)b * (4 + 6 * a.K);
+  const uint32_t n = o[0];
+  if (i >= a.K || (uint32_t)i >= n) return;
+  const uint32_t* s = stats_of(a, b) + kStatWords * kBuckets * i;
+  uint32_t sx = 0, sy = 0, xl = kNone, yl = kNone, xh = 0, yh = 0;
+#pragma unroll
+  for (int c = 0; c < kBuckets; ++c, s += kStatWords) {
+    sx += s[0];
+    sy += s[1];
+    xl = s[2] < xl ? s[2] : xl;
+    yl = s[3] < yl ? s[3] : yl;
+    xh = s[4] > xh ? s[4] : xh;
+    yh = s[5] > yh ? s[5] : yh;
+  }
+  uint32_t* r = o + 4 + 6 * i;
+  r[2] = sx;
+  r[3] = sy;
+  r[4] = xl | (yl << 16);
+  r[5] = xh | (yh << 16);
+}
+
+}  // namespace
+
+int class_regions_tile() { return kTile; }
+int class_regions_candidates() { return kCandidates; }
+
+size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w) {
+  const size_t N = (size_t)crop_h * (size_t)crop_w;
+  return (size_t)B * frame_words(N) * sizeof(uint32_t);
+}
+
+void class_regions(const ClassRegionsParams& p, hipStream_t s) {
+  const long long N = (long long)p.crop_h * p.crop_w;
+  if (p.B <= 0 || p.B > 65535 || p.crop_h <= 0 || p.crop_w <= 0 || p.crop_h > p.H ||
+      p.crop_w > p.W || N >= (1LL << 24) ||
+      N * (p.crop_w > p.crop_h ? p.crop_w : p.crop_h) >= (1LL << 32) || p.K < 1 || p.K > kMaxK ||
+      p.min_pixels < 1 || N / p.min_pixels > kCandidates)
+    check(hipErrorInvalidValue, "class_regions: bad shape");
+  CrArgs a;
+  a.labels = p.labels; a.out = p.out; a.ws = p.ws;
+  for (int i = 0; i < 8; ++i) a.cls[i] = p.classes[i];
+  a.H = p.H; a.W = p.W; a.crop_h = p.crop_h; a.crop_w = p.crop_w; a.K = p.K; a.N = (int)N;
+  a.min_pixels = (uint32_t)p.min_pixels;
+  const dim3 tiles(cdiv(p.crop_w, kTile), cdiv(p.crop_h, kTile), p.B);
+  hipLaunchKernelGGL(k_cr_local, tiles, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(k_cr_merge, tiles, dim3(64), 0, s, a);
+  const dim3 flat(cdiv(N, kThreads), p.B);
+  hipLaunchKernelGGL(k_cr_count, flat, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(k_cr_gather, flat, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(k_cr_select, dim3(p.B), dim3(kSelThreads), 0, s, a);
+  hipLaunchKernelGGL(k_cr_stats, tiles, dim3(kThreads), 0, s, a);
+  hipLaunchKernelGGL(k_cr_emit, dim3(p.B), dim3(kMaxK), 0, s, a);
+  check_launch("class_regions");
+}
+
+}  // namespace ssa

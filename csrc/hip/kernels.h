@@ -351,4 +351,24 @@ void mask_rle_copy_used(const uint32_t* src, uint32_t* dst, int B, int cap, hipS
 // 4-byte-aligned address, dst: any 2-byte-aligned one, n_macropixels >= 1.
 void yuv422_to_bgr(const uint8_t* src, uint8_t* dst, size_t n_macropixels, bool uyvy, hipStream_t s);
 
+// ---- class regions of the label maps (class_regions.hip) ----------------------
+// Per frame, the maximal 8-connected same-class pixel sets of labels[:crop_h, :crop_w] for
+// the classes whose bit is set in `classes` -> out[b] = uint32[4 + 6 K]: n_regions (those
+// of at least min_pixels pixels; the true number, may exceed K), N, crop_w, crop_h, then
+// for the first min(n_regions, K) regions by (pixels descending, root ascending) the words
+// (label << 24) | root, pixels, sum_x, sum_y, x_min | y_min << 16, x_max | y_max << 16.
+// Words past those are not written. N < 2^24, N * max(crop_w, crop_h) < 2^32, 1 <= K <= 256,
+// N / min_pixels <= class_regions_candidates().
+struct ClassRegionsParams {
+  const uint8_t* labels = nullptr;  // [B, H, W] (row stride W)
+  int B = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, K = 0, min_pixels = 0;
+  uint32_t classes[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit c of the 256-bit set: class c is served
+  uint32_t* out = nullptr;          // [B, 4 + 6 K]
+  uint32_t* ws = nullptr;           // class_regions_workspace_bytes(B, crop_h, crop_w)
+};
+size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w);
+int class_regions_tile();        // tile edge of the tile-local pass
+int class_regions_candidates();  // most regions that may pass in one frame
+void class_regions(const ClassRegionsParams& p, hipStream_t s);
+
 }  // namespace ssa

@@ -147,6 +147,37 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "truncated", 10, F.TYPE_BOOL)
     _field(m, "total_runs", 11, F.TYPE_UINT32)
 
+    m = fd.message_type.add(); m.name = "RegionRequest"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "max_regions", 2, F.TYPE_INT32)  # 0: all stored
+
+    # one 8-connected set of pixels of one class (postprocess/regions.py); the floats are
+    # fractions of the model input, like v1's area and centroid axes
+    m = fd.message_type.add(); m.name = "ClassRegion"
+    _field(m, "label", 1, F.TYPE_STRING)
+    _field(m, "class_id", 2, F.TYPE_INT32)
+    _field(m, "pixels", 3, F.TYPE_UINT32)
+    _field(m, "area", 4, F.TYPE_FLOAT)    # pixels / (model_width * model_height)
+    _field(m, "cx", 5, F.TYPE_FLOAT)      # (sum / pixels + 0.5) / model size
+    _field(m, "cy", 6, F.TYPE_FLOAT)
+    _field(m, "x_min", 7, F.TYPE_FLOAT)   # box edges / model size; the max edges are exclusive
+    _field(m, "y_min", 8, F.TYPE_FLOAT)
+    _field(m, "x_max", 9, F.TYPE_FLOAT)
+    _field(m, "y_max", 10, F.TYPE_FLOAT)
+
+    # the regions of the stream's latest frame, by (pixels descending, first pixel ascending)
+    m = fd.message_type.add(); m.name = "ClassRegions"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "frame_id", 2, F.TYPE_INT64)
+    _field(m, "timestamp", 3, F.TYPE_DOUBLE)
+    _field(m, "width", 4, F.TYPE_INT32)    # crop region, model-resolution pixels
+    _field(m, "height", 5, F.TYPE_INT32)
+    _field(m, "model_width", 6, F.TYPE_INT32)
+    _field(m, "model_height", 7, F.TYPE_INT32)
+    _field(m, "regions", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, ".sem_seg_server.v2.ClassRegion")
+    _field(m, "total_regions", 9, F.TYPE_UINT32)  # regions that passed; more than stored: truncated
+    _field(m, "truncated", 10, F.TYPE_BOOL)
+
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"
     E = ".sem_seg_server.Empty"
@@ -155,6 +186,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _method(svc, "GetStats", E, P + "Stats")
     _method(svc, "Health", E, P + "HealthStatus")
     _method(svc, "GetSegmentationMask", P + "MaskRequest", P + "SegmentationMask")
+    _method(svc, "GetClassRegions", P + "RegionRequest", P + "ClassRegions")
     return fd
 
 
@@ -211,6 +243,9 @@ Stats = _cls("sem_seg_server.v2.Stats")
 HealthStatus = _cls("sem_seg_server.v2.HealthStatus")
 MaskRequest = _cls("sem_seg_server.v2.MaskRequest")
 SegmentationMask = _cls("sem_seg_server.v2.SegmentationMask")
+RegionRequest = _cls("sem_seg_server.v2.RegionRequest")
+ClassRegion = _cls("sem_seg_server.v2.ClassRegion")
+ClassRegions = _cls("sem_seg_server.v2.ClassRegions")
 
 # ---- grpc.health.v1 ---------------------------------------------------------
 HealthCheckRequest = _cls("grpc.health.v1.HealthCheckRequest")
@@ -226,6 +261,7 @@ V2_METHODS = {
     "GetStats": (Empty, Stats),
     "Health": (Empty, HealthStatus),
     "GetSegmentationMask": (MaskRequest, SegmentationMask),
+    "GetClassRegions": (RegionRequest, ClassRegions),
 }
 
 

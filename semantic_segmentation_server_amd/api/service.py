@@ -72,8 +72,10 @@ class SemanticSegmentationV2Servicer:
     def __init__(self, hub: ResultHub, labels: Dict[int, str], num_detections: int = 3,
                  streams: Optional[list] = None, metrics=None,
                  health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None, *,
-                 serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0)):
+                 serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0),
+                 serve_regions: bool = False):
         self.hub = hub
+        self.serve_regions = bool(serve_regions)  # --serve_regions: GetClassRegions is enabled
         self.serve_masks = bool(serve_masks)  # --serve_masks: GetSegmentationMask is enabled
         self.model_size = model_size          # (width, height) of the label maps
         self.labels = labels
@@ -122,6 +124,45 @@ class SemanticSegmentationV2Servicer:
             height=int(m.words[3]), model_width=int(self.model_size[0]),
             model_height=int(self.model_size[1]), run_labels=labs, run_lengths=lens.tolist(),
             truncated=truncated, total_runs=total)
+
+    def GetClassRegions(self, request, context):
+        """The connected same-class regions of the stream's latest frame, largest first. The
+        producer stores integer words (postprocess/regions.py); the floats of the wire format
+        are computed here, for the one stream an RPC asks for."""
+        from ..postprocess import regions as RG
+        stream = int(request.stream_id)
+        if not self.serve_regions:
+            context.set_code(grpc.StatusCode.FAILED_PRECONDITION)
+            context.set_details("class regions are not enabled (start the server with --serve_regions)")
+            return P.ClassRegions()
+        if self.hub.get(stream) is None:
+            context.set_code(grpc.StatusCode.NOT_FOUND)
+            context.set_details(f"unknown stream_id {request.stream_id}")
+            return P.ClassRegions()
+        r = self.hub.regions(stream)
+        if r is None:
+            context.set_code(grpc.StatusCode.UNAVAILABLE)
+            context.set_details(f"no frame of stream {stream} collected yet")
+            return P.ClassRegions()
+        tab = RG.decode(r.words)
+        total = int(r.words[0])
+        if request.max_regions > 0:
+            tab = tab[:int(request.max_regions)]
+        mw, mh = float(self.model_size[0]), float(self.model_size[1])
+        out = []
+        for t in tab:
+            px = int(t["pixels"])
+            out.append(P.ClassRegion(
+                label=label_name(self.labels, int(t["label"])), class_id=int(t["label"]), pixels=px,
+                area=px / (mw * mh), cx=(int(t["sum_x"]) / px + 0.5) / mw,
+                cy=(int(t["sum_y"]) / px + 0.5) / mh, x_min=int(t["x_min"]) / mw,
+                y_min=int(t["y_min"]) / mh, x_max=(int(t["x_max"]) + 1) / mw,
+                y_max=(int(t["y_max"]) + 1) / mh))
+        return P.ClassRegions(
+            stream_id=stream, frame_id=r.frame_id, timestamp=r.ts, width=int(r.words[2]),
+            height=int(r.words[3]), model_width=int(self.model_size[0]),
+            model_height=int(self.model_size[1]), regions=out, total_regions=total,
+            truncated=len(out) < total)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

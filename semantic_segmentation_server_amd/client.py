@@ -93,6 +93,23 @@ def print_mask(m, lab: np.ndarray, labels: Dict[int, str]) -> None:
         print("  {:>3} {:<20} {:>8} px  {:5.1f} %".format(i, name, c, 100.0 * c / lab.size))
 
 
+def fetch_regions(target: str, stream: int = 0, max_regions: int = 0):
+    """The ClassRegions message of the stream's latest frame (v2 GetClassRegions)."""
+    with grpc.insecure_channel(target) as ch:
+        return SemanticSegmentationV2Stub(ch).GetClassRegions(
+            P.RegionRequest(stream_id=stream, max_regions=max_regions))
+
+
+def print_regions(m) -> None:
+    print("stream {} frame {} ts {:.3f}: {} regions in {} x {} (model {} x {}){}".format(
+        m.stream_id, m.frame_id, m.timestamp, m.total_regions, m.width, m.height, m.model_width,
+        m.model_height, " (truncated to {})".format(len(m.regions)) if m.truncated else ""))
+    for r in m.regions:
+        print("  {:>3} {:<20} {:>8} px  area {:.4f}  centre ({:.3f}, {:.3f})  box ({:.3f}, {:.3f}) - "
+              "({:.3f}, {:.3f})".format(r.class_id, r.label, r.pixels, r.area, r.cx, r.cy, r.x_min,
+                                       r.y_min, r.x_max, r.y_max))
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="sem_seg_server example client")
     p.add_argument("--target", default="localhost:50051")
@@ -105,7 +122,19 @@ def main(argv=None) -> int:
     p.add_argument("--mask_out", default=None, metavar="PATH.npy",
                    help="with --mask: save the decoded uint8 label map")
     p.add_argument("--labels", default=None, help="label file for --mask (default: Pascal VOC)")
+    p.add_argument("--regions", nargs="?", type=int, const=0, default=None, metavar="STREAM",
+                   help="fetch the class regions of the stream's latest frame (server run with "
+                        "--serve_regions) and print one line per region")
     a = p.parse_args(argv)
+    if a.regions is not None:
+        try:
+            m = fetch_regions(a.target, a.regions)
+        except grpc.RpcError as err:
+            print(err.details())
+            print("{}, {}".format(err.code().name, err.code().value))
+            return 1
+        print_regions(m)
+        return 0
     if a.mask is not None:
         from .labels import PASCAL_LABELS, load_labels
         try:

@@ -63,6 +63,10 @@ class Config:
     max_segments: int = 64                 # per-frame record capacity on device
     serve_masks: bool = False              # run-length encode every label map (v2 GetSegmentationMask)
     mask_max_runs: int = 32768             # run slots per frame; more runs truncate the mask
+    serve_regions: bool = False            # connected same-class regions of every label map (v2 GetClassRegions)
+    max_regions: int = 64                  # region records per frame (1 .. 256), largest first
+    region_min_area_ratio: float = 0.002   # smallest region served, as a share of input_size^2
+    region_classes: Optional[str] = None   # comma list of class ids / label names; None: all but 0
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -161,6 +165,17 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--mask_max_runs", type=int, default=d.mask_max_runs,
                    help="run slots per frame of the mask encoder; a frame with more runs is "
                         "served truncated")
+    p.add_argument("--serve_regions", action="store_true",
+                   help="find the 8-connected regions of every class in each frame's label map on "
+                        "the device and serve the latest ones per stream with box, centroid and "
+                        "area (v2 GetClassRegions); one GPU per process group")
+    p.add_argument("--max_regions", type=int, default=d.max_regions,
+                   help="region records per frame, largest first (1 .. 256)")
+    p.add_argument("--region_min_area_ratio", type=float, default=d.region_min_area_ratio,
+                   help="smallest region served, as a share of the model input's pixels")
+    p.add_argument("--region_classes", default=d.region_classes,
+                   help="comma list of class ids or label names whose regions are served "
+                        "(default: every class but 0)")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

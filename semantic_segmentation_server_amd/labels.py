@@ -49,6 +49,28 @@ def load_labels(path: str = PASCAL_LABELS) -> Dict[int, str]:
         return parse_labels(f.read())
 
 
+def parse_class_list(spec: str, labels: Dict[int, str]) -> list:
+    """Class ids of a comma list of ids and / or label names (``--region_classes``)."""
+    by_name = {v.strip().lower(): k for k, v in labels.items()}
+    out = []
+    for tok in str(spec).split(","):
+        tok = tok.strip()
+        if not tok:
+            continue
+        if tok.isdigit():
+            c = int(tok)
+        elif tok.lower() in by_name:
+            c = by_name[tok.lower()]
+        else:
+            raise ValueError(f"--region_classes: {tok!r} is neither a class id nor a label name")
+        if not 0 <= c <= 255:
+            raise ValueError(f"--region_classes: class id {c} outside 0 .. 255")
+        out.append(c)
+    if not out:
+        raise ValueError("--region_classes: empty list")
+    return out
+
+
 def label_name(labels: Dict[int, str], idx: int) -> str:
     """Name for a class id.
 

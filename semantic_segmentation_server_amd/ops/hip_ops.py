@@ -1243,6 +1243,48 @@ def yuv422_to_bgr(src: torch.Tensor, out: torch.Tensor, uyvy: bool = False) -> t
     return out
 
 
+REGION_TILE_W = REGION_TILE_H = 32  # tile of class_regions' tile-local pass (the module's REGION_TILE)
+REGION_CANDIDATES = 4096            # most regions that may pass in one frame (the module's)
+REGION_MAX_K = 256
+
+
+def class_regions_workspace_bytes(B, crop_h, crop_w) -> int:
+    return int(_hip_mod().class_regions_workspace_bytes(B, crop_h, crop_w))
+
+
+def class_regions(labels, out, ws, *, B, H, W, crop_h, crop_w, classes, min_pixels, K):
+    """Class regions of ``labels[:, :crop_h, :crop_w]`` (csrc/hip/class_regions.hip; the format
+    is postprocess/regions.py's): per frame ``out[b] = [n_regions, N, crop_w, crop_h, 6 words
+    per region ...]`` with the first ``min(n_regions, K)`` regions of at least ``min_pixels``
+    pixels by (pixels descending, root ascending). ``classes``: the served set (class ids or a
+    256-bit int mask). ``out``: uint32/int32 [B, 4 + 6 K]; ``ws``: at least
+    ``class_regions_workspace_bytes``."""
+    from ..postprocess import regions as RG
+    _chk(labels, torch.uint8, "labels", B * H * W)
+    if out.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f"out: expected uint32 or int32, got {out.dtype}")
+    _chk(out, out.dtype, "out")
+    if B < 1 or B > 65535:
+        raise ValueError(f"class_regions: bad batch {B}")
+    if not (1 <= crop_h <= H and 1 <= crop_w <= W):
+        raise ValueError(f"class_regions: crop {crop_h} x {crop_w} outside the {H} x {W} map")
+    RG.check_geometry(crop_w, crop_h, min_pixels, K)
+    if tuple(out.shape) != (B, 4 + 6 * K):
+        raise ValueError(f"out: shape {tuple(out.shape)} != ({B}, {4 + 6 * K})")
+    mask = RG.class_mask(classes)
+    m = _hip_mod()
+    if (m.REGION_TILE != REGION_TILE_W or m.REGION_CANDIDATES != REGION_CANDIDATES
+            or RG.REGION_CANDIDATES != REGION_CANDIDATES or RG.MAX_REGIONS != REGION_MAX_K):
+        raise RuntimeError("class_regions: REGION_TILE / REGION_CANDIDATES differ from the built module's")
+    _chk(ws, torch.uint8, "ws", class_regions_workspace_bytes(B, crop_h, crop_w))
+    w64 = (1 << 64) - 1
+    m.class_regions(_ptr(labels), B, H, W, crop_h, crop_w, mask & w64, (mask >> 64) & w64,
+                    (mask >> 128) & w64, (mask >> 192) & w64, int(min_pixels), int(K), _ptr(out),
+                    _ptr(ws), _stream())
+    _dbg('class_regions')
+    return out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

@@ -181,6 +181,13 @@ class DataParallelPipeline:
             raise ValueError("serve_masks is not supported in a multi-rank group (world size "
                              f"{ctx.world}): label masks are not gathered across ranks; run one "
                              "GPU, or the supervised server (independent workers)")
+        # --serve_regions: the same for each step's class-region words ([B, 4 + 6 K], about
+        # 1.5 KiB per frame: a plain async copy)
+        self.region_cap = int(getattr(engine, "region_cap", 0) or 0)
+        if self.region_cap and ctx.initialized and ctx.world > 1:
+            raise ValueError("serve_regions is not supported in a multi-rank group (world size "
+                             f"{ctx.world}): class regions are not gathered across ranks; run one "
+                             "GPU, or the supervised server (independent workers)")
         # lag L >= 1: step k collects step k-L's records, with L + 1 staging slots (so L + 1
         # steps can be in flight on a slot-parallel engine); SSA_PIPE_LAG overrides a
         # non-zero lag, else the engine may ask for more depth (slot-parallel: 2)
@@ -263,6 +270,9 @@ class DataParallelPipeline:
         self.local_mask = [torch.zeros((self.B, 4 + self.mask_cap), dtype=torch.int32,
                                        pin_memory=self.cuda) for _ in range(NS)] \
             if self.mask_cap else None
+        self.local_regions = [torch.zeros((self.B, 4 + 6 * self.region_cap), dtype=torch.int32,
+                                          pin_memory=self.cuda) for _ in range(NS)] \
+            if self.region_cap else None
         if gather == "host" and ctx.initialized:
             self.host_send = torch.empty((self.B, self.comb_width), dtype=torch.float32)
             self.host_gather = torch.empty((ctx.world, self.B, self.comb_width), dtype=torch.float32)
@@ -484,10 +494,13 @@ class DataParallelPipeline:
             self.frames_done += B * self.ctx.world
             if self.mask_cap and self.hub is not None and hasattr(self.hub, "push_masks"):
                 self.hub.push_masks(self.engine.host_masks(labels), self._node_meta(fids, strm, tss))
+            if self.region_cap and self.hub is not None and hasattr(self.hub, "push_regions"):
+                self.hub.push_regions(self.engine.host_regions(labels), self._node_meta(fids, strm, tss))
             return self.engine.records_from_labels(labels, fids, tss, strm)
         # the run words of this step's label maps: produced with the records (same graph,
         # same stream), copied with them, before the step's event
         mask = self.engine.mask_packed if self.mask_cap else None
+        regions = self.engine.region_packed if self.region_cap else None
         slot = self._rslot
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
@@ -500,12 +513,16 @@ class DataParallelPipeline:
                     self._d2h(packed, self.local_rec[slot])
                     if mask is not None:
                         self._d2h_mask(mask, self.local_mask[slot])
+                    if regions is not None:
+                        self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
                 ev = self._rec_ev[slot]  # per record slot: collected before the slot is reused
                 ev.record(rs)
             else:
                 self._d2h(packed, self.local_rec[slot])
                 if mask is not None:
                     self._d2h_mask(mask, self.local_mask[slot])
+                if regions is not None:
+                    self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
                 if self.cuda:
                     ev = self._rec_ev[slot]
                     ev.record(fast_cuda.current_stream(self.dev_index))
@@ -533,6 +550,8 @@ class DataParallelPipeline:
                 self._d2h(src, hdst)
             if mask is not None:  # world size 1 (checked at construction)
                 self._d2h_mask(mask, self.local_mask[slot])
+            if regions is not None:
+                self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
             # every rank (non-root ones too) records the step and goes through the lag
             # throttle: meta_host[slot] is rewritten only after the step that last used it
             # has been collected, i.e. after its H2D copy ran (VERDICT r3 Weak #4: non-root
@@ -743,6 +762,8 @@ class DataParallelPipeline:
 
     def _push_masks(self, slot: int, meta: np.ndarray) -> None:
         """Hand the collected step's run words (pinned, reused: the hub copies what it keeps)
-        and its frame metadata to the hub, if it takes masks."""
+        and its frame metadata to the hub, if it takes masks; the same for its region words."""
         if self.mask_cap and hasattr(self.hub, "push_masks"):
             self.hub.push_masks(self.local_mask[slot].numpy(), meta)
+        if self.region_cap and hasattr(self.hub, "push_regions"):
+            self.hub.push_regions(self.local_regions[slot].numpy(), meta)

@@ -19,8 +19,15 @@ from ..runtime.results import RECORD_DTYPE
 
 class DevicePostprocess:
     def __init__(self, device: torch.device, H: int, W: int, palette: np.ndarray, K: int = 64,
-                 bins: int = 32, thr: int = 127, mask_cap: int = 0):
+                 bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
+                 region_classes: int = 0, region_min_pixels: int = 1):
         self.device = device
+        # records per frame of the class-region kernels (class_regions.hip); 0: no kernel, no
+        # buffer, no launch. region_classes: the served 256-bit class set
+        self.region_cap = int(region_cap)
+        self.region_classes, self.region_min_pixels = int(region_classes), int(region_min_pixels)
+        self._region_bufs: Dict[tuple, tuple] = {}
+        self.last_regions = None
         # run slots per frame of the label-mask encoder (mask_rle.hip); 0: no encoder, no
         # buffer, no launch
         self.mask_cap = int(mask_cap)
@@ -67,14 +74,31 @@ class DevicePostprocess:
             self._mask_bufs[key] = (ws, words)
         return self._mask_bufs[key]
 
+    def region_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(workspace, [B, 4 + 6 region_cap] int32 region words) of the class-region kernels for
+        a batch of B frames: static and shared like ``mask_buffers``. The kernels of every run
+        initialise what they read of the workspace."""
+        key = (B, crop_w, crop_h)
+        if key not in self._region_bufs:
+            from . import regions as RG
+            RG.check_geometry(crop_w, crop_h, self.region_min_pixels, self.region_cap)
+            ws = torch.zeros(hip_ops.class_regions_workspace_bytes(B, crop_h, crop_w),
+                             dtype=torch.uint8, device=self.device)
+            words = torch.zeros((B, 4 + 6 * self.region_cap), dtype=torch.int32, device=self.device)
+            self._region_bufs[key] = (ws, words)
+        return self._region_bufs[key]
+
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
-            out: torch.Tensor = None, mask_out: torch.Tensor = None) -> torch.Tensor:
+            out: torch.Tensor = None, mask_out: torch.Tensor = None,
+            region_out: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
         shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
         the label maps are run-length encoded right after, on the same stream (so inside the
         same captured graph), into ``mask_buffers(B)`` or ``mask_out`` ([B, 4 + mask_cap]
-        int32 rows); ``last_mask`` is the buffer written."""
+        int32 rows); ``last_mask`` is the buffer written. With ``region_cap`` the class regions
+        follow on the same stream, into ``region_buffers(B)`` or ``region_out`` ([B, 4 + 6
+        region_cap] int32 rows); ``last_regions`` is the buffer written."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -94,6 +118,14 @@ class DevicePostprocess:
             hip_ops.mask_rle(labels, words, mws, B=B, H=self.H, W=self.W, crop_h=crop_h,
                              crop_w=crop_w, cap=self.mask_cap)
             self.last_mask = words
+        if self.region_cap:
+            rws, words = self.region_buffers(B, crop_w, crop_h)
+            if region_out is not None:
+                words = region_out
+            hip_ops.class_regions(labels, words, rws, B=B, H=self.H, W=self.W, crop_h=crop_h,
+                                  crop_w=crop_w, classes=self.region_classes,
+                                  min_pixels=self.region_min_pixels, K=self.region_cap)
+            self.last_regions = words
         return rec
 
     def fetch(self, rec: torch.Tensor, frame_ids: Sequence[int], ts: Sequence[float],
@@ -108,11 +140,14 @@ class DevicePostprocess:
         return unpack_records(h.numpy(), self.K, frame_ids, ts, streams)
 
     def fetch_masks(self, words: torch.Tensor) -> np.ndarray:
-        """Synchronous D2H of the run words of ``run`` -> uint32 [B, 4 + mask_cap] (a copy)."""
-        B = words.shape[0]
-        h = self._mask_host.get(B)
+        """Synchronous D2H of the run words (or the region words) of ``run`` -> uint32 of the
+        same shape (a copy)."""
+        key = tuple(words.shape)
+        h = self._mask_host.get(key)
         if h is None:
-            h = self._mask_host[B] = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
+            h = self._mask_host[key] = torch.empty(words.shape, dtype=torch.int32, pin_memory=True)
         h.copy_(words, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return h.numpy().view(np.uint32).copy()
+
+    fetch_regions = fetch_masks  # the same: a uint32 row per frame with a 4-word header

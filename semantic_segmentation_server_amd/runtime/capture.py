@@ -1,6 +1,6 @@
 """Captured steps of the engine, one class per capture form: the hipGraphs of one frame buffer
 and the static outputs they write (``labels``; ``post``: packed records or None; ``mask``:
---serve_masks run words or None). ``replay()`` issues that form's replays, waits and event
+--serve_masks run words or None; ``regions``: --serve_regions region words or None). ``replay()`` issues that form's replays, waits and event
 records; after ``consumed`` the buffer may be refilled (None: the model ran on the caller's stream).
 
 With a raw pixel format (``eng.frame_channels == 2``) the frame buffer holds packed 4:2:2 bytes
@@ -42,12 +42,12 @@ def _graph(fn):
 
 
 class WholeStep:
-    """One graph, model + post-processing (+ masks), on the caller's stream."""
+    """One graph, model + post-processing (+ masks, + regions), on the caller's stream."""
 
     def __init__(self, eng, frames):
         self.frames, self.consumed = frames, None
         self.bgr = bgr = eng.bgr_buffer(frames)
-        self.graph, (self.labels, self.post, self.mask) = _graph(lambda: eng._step_outputs(frames, bgr))
+        self.graph, (self.labels, self.post, self.mask, self.regions) = _graph(lambda: eng._step_outputs(frames, bgr))
 
     def replay(self) -> None:
         self.graph.replay()
@@ -55,7 +55,7 @@ class WholeStep:
 
 class SplitStep:
     """The model graph on the caller's stream, the post-processing graph (records, then the
-    run-length masks) on the engine's ``result_stream``."""
+    run-length masks, then the class regions: one chain) on the engine's ``result_stream``."""
 
     def __init__(self, eng, frames, part: int = 0):
         hm, dev = eng._hip_model, eng.device
@@ -74,7 +74,7 @@ class SplitStep:
             self.model, _ = _graph(segment)
         else:
             self.model, _ = _graph(lambda: lab.copy_(eng._infer_eager(frames, bgr)))
-        self.post_graph, (self.post, self.mask) = _graph(lambda: eng._post_and_mask(lab))
+        self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab))
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
     def replay(self) -> None:
@@ -134,10 +134,13 @@ class PartsStep:
         self.post = post = torch.zeros((B, 1 + 5 * eng.cfg.max_segments), dtype=torch.float32, device=dev)
         self.mask = mask = torch.zeros((B, 4 + eng.mask_cap), dtype=torch.int32,
                                        device=dev) if eng.mask_cap else None
+        self.regions = reg = torch.zeros((B, 4 + 6 * eng.region_cap), dtype=torch.int32,
+                                         device=dev) if eng.region_cap else None
         parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
                                                 eng.lut_x, eng.lut_y, out=lab[sl], part=i),
                   lambda sl=sl: eng._device_post(lab[sl], out=post[sl],
-                                                 mask_out=mask[sl] if mask is not None else None))
+                                                 mask_out=mask[sl] if mask is not None else None,
+                                                 region_out=reg[sl] if reg is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)
         for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
             run()

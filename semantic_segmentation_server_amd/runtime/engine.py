@@ -123,6 +123,21 @@ class Engine:
             MR.check_geometry(self.W, self.H, self.mask_cap)  # every crop is within H x W
         self.mask_packed: Optional[torch.Tensor] = None
         self.masks: Optional[np.ndarray] = None
+        # --serve_regions: records per frame of the class-region kernels (0 = off: no kernel,
+        # no buffer); region_packed / regions: as mask_packed / masks, [B, 4 + 6 cap] words
+        # (postprocess/regions.py)
+        self.region_cap = int(cfg.max_regions) if cfg.serve_regions else 0
+        self.region_mask, self.region_min_pixels = 0, 1
+        if cfg.serve_regions:
+            from ..labels import parse_class_list
+            from ..postprocess import regions as RG
+            self.region_mask = (RG.class_mask(parse_class_list(cfg.region_classes, load_labels(cfg.labels)))
+                                if cfg.region_classes else RG.default_classes(cfg.num_classes))
+            self.region_min_pixels = RG.min_pixels_for(cfg.region_min_area_ratio, self.H, self.W)
+            # every crop is within H x W, and holds no more candidates than the whole map
+            RG.check_geometry(self.W, self.H, self.region_min_pixels, self.region_cap)
+        self.region_packed: Optional[torch.Tensor] = None
+        self.regions: Optional[np.ndarray] = None
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -219,13 +234,16 @@ class Engine:
         return R.upsample_argmax(logits, self.H, self.W)
 
     def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
-                     mask_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._post_and_mask(labels, out, mask_out)[0]  # the records alone
+                     mask_out: Optional[torch.Tensor] = None,
+                     region_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._post_and_mask(labels, out, mask_out, region_out)[0]  # the records alone
 
     def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
-                       mask_out: Optional[torch.Tensor] = None):
-        """(device records of ``labels``, with ``mask_cap`` their run-length masks else None),
-        the masks right after the records on the same stream: one captured graph holds both."""
+                       mask_out: Optional[torch.Tensor] = None,
+                       region_out: Optional[torch.Tensor] = None):
+        """(device records of ``labels``, with ``mask_cap`` their run-length masks else None,
+        with ``region_cap`` their class regions else None), each right after the other on the
+        same stream: one captured graph, a chain, holds all."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -233,10 +251,13 @@ class Engine:
             self._hip_post = DevicePostprocess(self.device, self.H, self.W, self.palette,
                                                self.cfg.max_segments,
                                                bins=max(1, min(256, self.cfg.num_classes)),
-                                               mask_cap=self.mask_cap)
+                                               mask_cap=self.mask_cap, region_cap=self.region_cap,
+                                               region_classes=self.region_mask,
+                                               region_min_pixels=self.region_min_pixels)
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
-                                 mask_out=mask_out)
-        return rec, (self._hip_post.last_mask if self.mask_cap else None)
+                                 mask_out=mask_out, region_out=region_out)
+        return (rec, self._hip_post.last_mask if self.mask_cap else None,
+                self._hip_post.last_regions if self.region_cap else None)
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
@@ -251,8 +272,20 @@ class Engine:
             MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
         return out
 
+    def host_regions(self, labels) -> np.ndarray:
+        """uint32 [B, 4 + 6 cap] region words of host label maps by the numpy definition
+        (postprocess/regions.py): the CPU path, and a GPU without device post-processing."""
+        from ..postprocess import regions as RG
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        out = np.zeros((lab.shape[0], 4 + 6 * self.region_cap), np.uint32)
+        for b in range(lab.shape[0]):
+            RG.encode(lab[b], self.crop_w, self.crop_h, self.region_mask, self.region_min_pixels,
+                      self.region_cap, out=out[b])
+        return out
+
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
-        """One eager step: (labels, packed records or None, mask run words or None)."""
+        """One eager step: (labels, packed records or None, mask run words or None, region
+        words or None)."""
         labels = self._infer_eager(frames, bgr)
         if self._use_device_post():
             return (labels, *self._post_and_mask(labels))
@@ -260,11 +293,13 @@ class Engine:
         # post-processing path encodes them where it brings the label maps to the host
         host = not self.is_cuda
         mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
+        regions = torch.from_numpy(self.host_regions(labels).view(np.int32)) \
+            if host and self.region_cap else None
         post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
-        return labels, post, mask
+        return labels, post, mask, regions
 
     def _step_device(self, frames: torch.Tensor):
-        labels, post, self.mask_packed = self._step_outputs(frames)
+        labels, post, self.mask_packed, self.region_packed = self._step_outputs(frames)
         return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
@@ -393,7 +428,7 @@ class Engine:
             step.frames.copy_(frames, non_blocking=True)
         step.replay()
         # written by the replay, like the records; and when the frame buffer may be refilled
-        self.mask_packed, self.last_consumed = step.mask, step.consumed
+        self.mask_packed, self.region_packed, self.last_consumed = step.mask, step.regions, step.consumed
         return step.labels, step.post
 
     # ------------------------------------------------------------ post/host
@@ -448,6 +483,8 @@ class Engine:
                                 _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))
             if self.mask_cap:
                 self.masks = self.host_masks(labels)
+            if self.region_cap:
+                self.regions = self.host_regions(labels)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         with torch.cuda.stream(self.stream):
@@ -462,11 +499,15 @@ class Engine:
                                                 _per_frame(streams, len(frame_ids)), self.W, self.H)
                 if self.mask_cap:  # same stream, after the records: one more small D2H
                     self.masks = self._hip_post.fetch_masks(self.mask_packed)
+                if self.region_cap:
+                    self.regions = self._hip_post.fetch_regions(self.region_packed)
             else:
                 recs = None
         self.stream.synchronize()
         if self.mask_cap and post is None:
             self.masks = self.host_masks(labels)
+        if self.region_cap and post is None:
+            self.regions = self.host_regions(labels)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

@@ -137,8 +137,33 @@ class StoredMask(NamedTuple):
     words: np.ndarray  # uint32[4 + stored runs] (postprocess/mask_rle.py)
 
 
+class StoredRegions(NamedTuple):
+    """A stream's latest class regions: the words are the hub's own copy."""
+    frame_id: int
+    ts: float
+    words: np.ndarray  # uint32[4 + 6 * stored regions] (postprocess/regions.py)
+
+
+def latest_rows(rows: np.ndarray, meta: np.ndarray, unit: int = 1):
+    """Of a collected batch of uint32 rows with a 4-word header whose word 0 counts the
+    payload entries (``unit`` words each; run words: 1, region words: 6), yield per stream
+    its LAST frame as (stream, frame id, ts, the row's used words: a view). ``meta``: [F, 3]
+    (frame id, stream, capture ts) in the rows' order."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.uint32:
+        rows = rows.view(np.uint32)
+    cap = (rows.shape[1] - 4) // unit
+    last: Dict[int, int] = {}
+    for i in range(len(rows)):
+        last[int(meta[i, 1])] = i
+    for st, i in last.items():
+        used = 4 + unit * min(int(rows[i, 0]), cap)
+        yield st, int(meta[i, 0]), float(meta[i, 2]), rows[i, :used]
+
+
 class ResultHub:
-    """One ``ResultBuffer`` per stream id (and, with --serve_masks, its latest mask)."""
+    """One ``ResultBuffer`` per stream id (and, with --serve_masks, its latest mask; with
+    --serve_regions, its latest class regions)."""
 
     def __init__(self, num_streams: int = 1, maxlen: Optional[int] = 4096):
         self.buffers: Dict[int, ResultBuffer] = {
@@ -146,6 +171,7 @@ class ResultHub:
         self.maxlen = maxlen
         self._lock = threading.Lock()
         self._masks: Dict[int, StoredMask] = {}
+        self._regions: Dict[int, StoredRegions] = {}
 
     def get(self, stream: int) -> Optional[ResultBuffer]:
         """The stream's buffer, or None for a stream id the hub does not serve (RPC
@@ -191,21 +217,32 @@ class ResultHub:
         a pinned buffer the producer reuses); ``meta``: [F, 3] (frame id, stream, capture
         ts) in the same order. Of several frames of one stream only the last is copied,
         and only its ``4 + min(n_runs, cap)`` used words."""
-        rows = np.asarray(rows)
-        if rows.dtype != np.uint32:
-            rows = rows.view(np.uint32)
-        cap = rows.shape[1] - 4
-        last: Dict[int, int] = {}
-        for i in range(len(rows)):
-            last[int(meta[i, 1])] = i
-        for st, i in last.items():
-            used = 4 + min(int(rows[i, 0]), cap)
-            self.put_mask(st, int(meta[i, 0]), float(meta[i, 2]), rows[i, :used])
+        for st, fid, ts, words in latest_rows(rows, meta):
+            self.put_mask(st, fid, ts, words)
 
     def mask(self, stream: int) -> Optional["StoredMask"]:
         """The stream's latest mask (frame_id, ts, words), or None before the first one."""
         with self._lock:
             return self._masks.get(int(stream))
+
+    # ---- class regions (--serve_regions): the LATEST region words per stream
+    def put_regions(self, stream: int, frame_id: int, ts: float, words: np.ndarray) -> None:
+        """Store a COPY of ``words`` (header + stored records, postprocess/regions.py) as the
+        stream's latest regions."""
+        r = StoredRegions(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True))
+        with self._lock:
+            self._regions[int(stream)] = r
+
+    def push_regions(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """As ``push_masks`` for [F, 4 + 6 K] region words: of several frames of one stream
+        only the last is copied, and only its ``4 + 6 * min(n_regions, K)`` used words."""
+        for st, fid, ts, words in latest_rows(rows, meta, 6):
+            self.put_regions(st, fid, ts, words)
+
+    def regions(self, stream: int) -> Optional["StoredRegions"]:
+        """The stream's latest regions (frame_id, ts, words), or None before the first ones."""
+        with self._lock:
+            return self._regions.get(int(stream))
 
     @property
     def depth(self) -> int:

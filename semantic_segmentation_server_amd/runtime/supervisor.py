@@ -23,9 +23,10 @@ inside a write cannot leave a lock held or half a message behind for its success
   publishes a chunk by advancing the write index after the rows, the parent advances
   the read index after copying them out. A full ring drops the chunk (counted).
 * masks (``--serve_masks``): per stream, two slots of run words in a second shared-memory
-  block (``_MaskChannel``), each guarded by a sequence counter (odd while the worker
+  block (``_WordChannel``), each guarded by a sequence counter (odd while the worker
   writes it); the parent copies the newest complete slot into its hub and keeps its
-  previous copy when it meets a slot being written.
+  previous copy when it meets a slot being written. Class regions (``--serve_regions``)
+  travel the same way, in a channel of their own with six words per entry.
 * progress: the ring header carries the worker's step count and the time of its last
   step, written by the worker's producer loop itself -- liveness is step PROGRESS, not a
   timer thread, so a worker whose GPU hangs (producer stuck in a synchronize) goes stale
@@ -72,7 +73,7 @@ from typing import List, Optional
 import numpy as np
 
 from ..config import Config
-from .results import RECORD_DTYPE
+from .results import RECORD_DTYPE, latest_rows
 
 log = logging.getLogger(__name__)
 
@@ -171,13 +172,15 @@ class _RecordRing:
                 pass
 
 
-class _MaskChannel:
-    """The latest label mask per stream (postprocess/mask_rle.py run words) in POSIX shared
-    memory, single writer (the worker) / single reader (the parent).
+class _WordChannel:
+    """The latest row of words per stream -- a 4-word header whose word 0 counts the entries,
+    then ``unit`` words per entry: a label mask (postprocess/mask_rle.py run words, unit 1) or
+    a frame's class regions (postprocess/regions.py, unit 6) -- in POSIX shared memory, single
+    writer (the worker) / single reader (the parent).
 
-    Block header (int64): 0 streams, 1 cap, 2 first (global) stream id. Per stream two
-    slots, each [int64 seq, int64 frame id, float64 ts, int64 pad | uint32[4 + cap]]. The
-    writer alternates a stream's slots: it sets the slot's seq to the odd 2k + 1, writes
+    Block header (int64): 0 streams, 1 cap (entries), 2 first (global) stream id, 3 unit. Per
+    stream two slots, each [int64 seq, int64 frame id, float64 ts, int64 pad | uint32[4 + cap *
+    unit]]. The writer alternates a stream's slots: it sets the slot's seq to the odd 2k + 1, writes
     the payload, then the even 2k + 2 (k: the stream's write count; x86-64 keeps stores in
     program order). The reader takes a slot only if its seq is even, newer than the last
     one it delivered and unchanged after the copy; otherwise it keeps its previous copy and
@@ -186,10 +189,11 @@ class _MaskChannel:
 
     HDR = 4
 
-    def __init__(self, streams: int = 1, cap: int = 2, first: int = 0, name: Optional[str] = None):
+    def __init__(self, streams: int = 1, cap: int = 2, first: int = 0, name: Optional[str] = None,
+                 unit: int = 1):
         self.owner = name is None
         if self.owner:
-            nbytes = self.HDR * 8 + int(streams) * 2 * self._slot_bytes(int(cap))
+            nbytes = self.HDR * 8 + int(streams) * 2 * self._slot_bytes(int(cap) * int(unit))
             self.shm = shared_memory.SharedMemory(create=True, size=nbytes)
         else:
             self.shm = shared_memory.SharedMemory(name=name)
@@ -197,15 +201,17 @@ class _MaskChannel:
         self.hdr = np.ndarray((self.HDR,), dtype=np.int64, buffer=buf)
         if self.owner:
             np.ndarray((nbytes,), dtype=np.uint8, buffer=buf)[:] = 0
-            self.hdr[0], self.hdr[1], self.hdr[2] = streams, cap, first
+            self.hdr[0], self.hdr[1], self.hdr[2], self.hdr[3] = streams, cap, first, unit
         self.S, self.cap, self.first = int(self.hdr[0]), int(self.hdr[1]), int(self.hdr[2])
-        sb = self._slot_bytes(self.cap)
+        self.unit = int(self.hdr[3])
+        sb = self._slot_bytes(self.cap * self.unit)
         self.meta, self.ts, self.words = [], [], []
         for i in range(self.S * 2):
             off = self.HDR * 8 + i * sb
             self.meta.append(np.ndarray((4,), dtype=np.int64, buffer=buf, offset=off))
             self.ts.append(np.ndarray((1,), dtype=np.float64, buffer=buf, offset=off + 16))
-            self.words.append(np.ndarray((4 + self.cap,), dtype=np.uint32, buffer=buf, offset=off + 32))
+            self.words.append(np.ndarray((4 + self.cap * self.unit,), dtype=np.uint32, buffer=buf,
+                                         offset=off + 32))
         self._writes = [0] * self.S      # worker side: writes per stream
         self._delivered = [0] * self.S   # parent side: seq of the last mask taken per stream
 
@@ -220,7 +226,7 @@ class _MaskChannel:
     # ---- worker side
     def write(self, stream: int, frame_id: int, ts: float, words: np.ndarray) -> None:
         s = int(stream) - self.first
-        if not 0 <= s < self.S or len(words) > 4 + self.cap:
+        if not 0 <= s < self.S or len(words) > 4 + self.cap * self.unit:
             return
         k = self._writes[s]
         i = 2 * s + (k & 1)
@@ -243,7 +249,7 @@ class _MaskChannel:
                 if seq & 1 or seq <= self._delivered[s] or (best is not None and seq < best[0]):
                     continue
                 fid, ts = int(self.meta[i][1]), float(self.ts[i][0])
-                used = 4 + min(int(self.words[i][0]), self.cap)
+                used = 4 + self.unit * min(int(self.words[i][0]), self.cap)
                 w = self.words[i][:used].copy()
                 if int(self.meta[i][0]) != seq:  # rewritten under the copy: keep the previous one
                     continue
@@ -267,13 +273,18 @@ class _MaskChannel:
                 pass
 
 
+_MaskChannel = _WordChannel  # unit 1: run words
+
+
 class _RingHub:
     """The worker's stand-in for the ResultHub: pushes go to the shared-memory ring (and
-    the latest masks to the incarnation's mask channel)."""
+    the latest masks / regions to the incarnation's channels)."""
 
-    def __init__(self, ring: _RecordRing, masks: Optional[_MaskChannel] = None):
+    def __init__(self, ring: _RecordRing, masks: Optional[_WordChannel] = None,
+                 regions: Optional[_WordChannel] = None):
         self.ring = ring
         self.masks = masks
+        self.region_ch = regions
         self.buffers = {}
         self.depth = 0
 
@@ -285,15 +296,15 @@ class _RingHub:
         """As ResultHub.push_masks: per stream of the batch, its last frame's used words."""
         if self.masks is None:
             return
-        rows = np.asarray(rows)
-        if rows.dtype != np.uint32:
-            rows = rows.view(np.uint32)
-        last = {}
-        for i in range(len(rows)):
-            last[int(meta[i, 1])] = i
-        for st, i in last.items():
-            used = 4 + min(int(rows[i, 0]), rows.shape[1] - 4)
-            self.masks.write(st, int(meta[i, 0]), float(meta[i, 2]), rows[i, :used])
+        for st, fid, ts, words in latest_rows(rows, meta):
+            self.masks.write(st, fid, ts, words)
+
+    def push_regions(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """As ResultHub.push_regions."""
+        if self.region_ch is None:
+            return
+        for st, fid, ts, words in latest_rows(rows, meta, self.region_ch.unit):
+            self.region_ch.write(st, fid, ts, words)
 
 
 def _fault_for(spec: Optional[str], rank: int, incarnation: int):
@@ -309,7 +320,8 @@ def _fault_for(spec: Optional[str], rank: int, incarnation: int):
 
 
 def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnation: int,
-                 max_steps: Optional[int], mask_name: Optional[str] = None) -> None:
+                 max_steps: Optional[int], mask_name: Optional[str] = None,
+                 region_name: Optional[str] = None) -> None:
     """Child process: rank ``rank``'s producer, reporting through the ring and ``q``."""
     logging.basicConfig(level=getattr(logging, cfg.log_level.upper(), logging.INFO),
                         format=f"%(asctime)s %(levelname)s worker{rank}: %(message)s")
@@ -322,7 +334,8 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     from .pipeline import Producer
     from .sources import make_source
     ring = _RecordRing(name=ring_name)
-    masks = _MaskChannel(name=mask_name) if mask_name else None
+    masks = _WordChannel(name=mask_name) if mask_name else None
+    regions = _WordChannel(name=region_name) if region_name else None
     metrics = Metrics()
     device = None
     if cfg.device != "cpu" and torch.cuda.is_available() and torch.cuda.device_count() > rank:
@@ -333,7 +346,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
                            cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank,
                            pixel_format=cfg.pixel_format)
                for s in range(S)]
-    prod = Producer(engine, sources, _RingHub(ring, masks), metrics, cfg.batch, max_steps=max_steps)
+    prod = Producer(engine, sources, _RingHub(ring, masks, regions), metrics, cfg.batch, max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
 
     def on_step(n: int) -> None:  # step progress, published by the producer thread itself
@@ -382,7 +395,8 @@ class _Worker:
         self.incarnation = -1
         self.proc = None
         self.ring: Optional[_RecordRing] = None
-        self.masks: Optional[_MaskChannel] = None
+        self.masks: Optional[_WordChannel] = None
+        self.regions: Optional[_WordChannel] = None
         self.q = None
         self.up = False
         self.started = 0.0
@@ -431,6 +445,7 @@ class SupervisedServer:
         S.add_v2_servicer(S.SemanticSegmentationV2Servicer(self.hub, labels, cfg.num_detections,
                                                            streams, self.metrics, self._health,
                                                            serve_masks=cfg.serve_masks,
+                                                           serve_regions=cfg.serve_regions,
                                                            model_size=(cfg.input_size, cfg.input_size)),
                           self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
@@ -472,11 +487,14 @@ class SupervisedServer:
         w.up = False
         w.q = self._ctx.Queue()
         w.ring = _RecordRing(self.ring_rows)
-        w.masks = _MaskChannel(self.S, int(self.cfg.mask_max_runs), w.rank * self.S) \
+        w.masks = _WordChannel(self.S, int(self.cfg.mask_max_runs), w.rank * self.S) \
             if self.cfg.serve_masks else None
+        w.regions = _WordChannel(self.S, int(self.cfg.max_regions), w.rank * self.S, unit=6) \
+            if self.cfg.serve_regions else None
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
-                                         self.max_steps, w.masks.name if w.masks is not None else None),
+                                         self.max_steps, w.masks.name if w.masks is not None else None,
+                                         w.regions.name if w.regions is not None else None),
                                    daemon=True)
         w.proc.start()
         w.started = time.time()
@@ -511,6 +529,9 @@ class SupervisedServer:
         if w.masks is not None:
             for stream, fid, ts, words in w.masks.pull():
                 self.hub.put_mask(stream, fid, ts, words)
+        if w.regions is not None:
+            for stream, fid, ts, words in w.regions.pull():
+                self.hub.put_regions(stream, fid, ts, words)
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
@@ -587,6 +608,9 @@ class SupervisedServer:
         if w.masks is not None:
             w.masks.close()
             w.masks = None
+        if w.regions is not None:
+            w.regions.close()
+            w.regions = None
         if w.q is not None:
             try:
                 w.q.close()

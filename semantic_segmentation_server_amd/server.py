@@ -63,6 +63,7 @@ class Server:
         self.v2 = S.SemanticSegmentationV2Servicer(self.hub, self.labels, cfg.num_detections,
                                                    streams, self.metrics, self._health,
                                                    serve_masks=cfg.serve_masks,
+                                                   serve_regions=cfg.serve_regions,
                                                    model_size=(cfg.input_size, cfg.input_size))
         S.add_v1_servicer(self.v1, self.grpc_server)
         S.add_v2_servicer(self.v2, self.grpc_server)
