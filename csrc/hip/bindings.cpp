@@ -408,6 +408,11 @@ PYBIND11_MODULE(_hip, m) {
     upsample_argmax(P<const bf16>(logits), P<uint8_t>(labels), B, h, w, K, ldk, H, W, S(stream),
                     variant);
   });
+  m.def("upsample_argmax_conf", [](uintptr_t logits, uintptr_t labels, uintptr_t conf, int B, int h,
+                                   int w, int K, int ldk, int H, int W, uintptr_t stream) {
+    upsample_argmax_conf(P<const bf16>(logits), P<uint8_t>(labels), P<uint8_t>(conf), B, h, w, K, ldk,
+                         H, W, S(stream));
+  });
 
   m.def("post_workspace_bytes", &post_workspace_bytes);
   m.def("copy_to_host", [](uintptr_t src, uintptr_t dst, long long nbytes, uintptr_t stream) {
@@ -450,12 +455,14 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.attr("MASK_RLE_CHUNK") = mask_rle_chunk();
 
-  m.def("class_regions_workspace_bytes", &class_regions_workspace_bytes);
+  m.def("class_regions_workspace_bytes", &class_regions_workspace_bytes, py::arg("B"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("conf") = false);
   m.def("class_regions",
         [](uintptr_t labels, int B, int H, int W, int crop_h, int crop_w, uint64_t c0, uint64_t c1,
            uint64_t c2, uint64_t c3, int min_pixels, int K, uintptr_t out, uintptr_t ws,
-           uintptr_t stream) {
+           uintptr_t stream, uintptr_t conf) {
           ClassRegionsParams p;
+          p.conf = P<const uint8_t>(conf);
           p.labels = P<const uint8_t>(labels); p.B = B; p.H = H; p.W = W;
           p.crop_h = crop_h; p.crop_w = crop_w; p.min_pixels = min_pixels; p.K = K;
           const uint64_t c[4] = {c0, c1, c2, c3};  // the 256-bit class set, 64 bits a word
@@ -465,7 +472,8 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("labels"), py::arg("B"), py::arg("H"), py::arg("W"), py::arg("crop_h"),
         py::arg("crop_w"), py::arg("c0"), py::arg("c1"), py::arg("c2"), py::arg("c3"),
-        py::arg("min_pixels"), py::arg("K"), py::arg("out"), py::arg("ws"), py::arg("stream"));
+        py::arg("min_pixels"), py::arg("K"), py::arg("out"), py::arg("ws"), py::arg("stream"),
+        py::arg("conf") = 0);
   m.attr("REGION_TILE") = class_regions_tile();
   m.attr("REGION_CANDIDATES") = class_regions_candidates();
 

@@ -44,6 +44,14 @@
 //                otherwise send every tile's atomics to one address, where they queue.
 //   k_cr_emit    folds a slot's copies and packs them into words 2 .. 5 of the records.
 // All sums are integer: the result is exact and independent of any arrival order.
+//
+// With a confidence plane (conf[B, H, W], one code per pixel beside the labels) select, stats
+// and emit run in their CONF form and a record has a seventh word, sum_conf: the sum of the
+// codes of the region's pixels (< 2^24 x 255 < 2^32). The run's closed form does not apply: the
+// lanes of a run add their codes in the wave (a segmented shuffle reduction) and the run's
+// first lane sends one LDS atomic, to a seventh accumulator plane. The global sums live in
+// kBuckets x kMaxK words per frame BEHIND the workspace of the form without confidence, whose
+// layout, code path and output are unchanged.
 #include "kernels.h"
 
 namespace ssa {
@@ -68,6 +76,8 @@ struct CrArgs {
   uint32_t cls[8];
   int H, W, crop_h, crop_w, K, N;
   uint32_t min_pixels;
+  const uint8_t* conf;  // CONF forms only
+  uint32_t* csum;       // CONF forms only: [B][kMaxK][kBuckets] behind the B frames of ws
 };
 
 constexpr size_t kTailWords = (size_t)kStatWords * kMaxK * kBuckets + 2 + 2 * (size_t)kCandidates;
@@ -79,6 +89,10 @@ __device__ __forceinline__ uint32_t* stats_of(const CrArgs& a, int b) { return p
 // [0]: number of candidates, [2 + 2 j], [3 + 2 j]: pixels and root of candidate j
 __device__ __forceinline__ uint32_t* cand_of(const CrArgs& a, int b) {
   return stats_of(a, b) + kStatWords * kMaxK * kBuckets;
+}
+
+__device__ __forceinline__ uint32_t* csum_of(const CrArgs& a, int b) {
+  return a.csum + (size_t)b * kMaxK * kBuckets;
 }
 
 __device__ __forceinline__ bool served(const CrArgs& a, int l) { return (a.cls[l >> 5] >> (l & 31)) & 1u; }
@@ -302,7 +316,9 @@ __global__ __launch_bounds__(kThreads) void k_cr_gather(CrArgs a) {
 }
 
 // ---- 5. select and order -------------------------------------------------------------------
+template <bool CONF>
 __global__ __launch_bounds__(kSelThreads) void k_cr_select(CrArgs a) {
+  constexpr int RW = CONF ? 7 : 6;  // words of a record
   __shared__ unsigned long long key[kCandidates];
   const int b = blockIdx.x, tid = threadIdx.x;
   uint32_t* cnt = cnt_of(a, b);
@@ -331,7 +347,7 @@ __global__ __launch_bounds__(kSelThreads) void k_cr_select(CrArgs a) {
       __syncthreads();
     }
   }
-  uint32_t* o = a.out + (size_t)b * (4 + 6 * a.K);
+  uint32_t* o = a.out + (size_t)b * (4 + RW * a.K);
   uint32_t* st = stats_of(a, b);
   const uint8_t* img = a.labels + (size_t)b * a.H * a.W;
   const int kept = n < a.K ? n : a.K;
@@ -339,13 +355,14 @@ __global__ __launch_bounds__(kSelThreads) void k_cr_select(CrArgs a) {
     const unsigned long long k = key[i];
     const uint32_t root = ~(uint32_t)k, pixels = (uint32_t)(k >> 32);
     const int y = (int)(root / (uint32_t)a.crop_w), x = (int)(root - (uint32_t)y * a.crop_w);
-    o[4 + 6 * i] = ((uint32_t)img[(size_t)y * a.W + x] << 24) | root;
-    o[4 + 6 * i + 1] = pixels;
+    o[4 + RW * i] = ((uint32_t)img[(size_t)y * a.W + x] << 24) | root;
+    o[4 + RW * i + 1] = pixels;
     cnt[root] = kSlotBit | (uint32_t)i;
   }
   for (int j = tid; j < kept * kBuckets; j += kSelThreads) {  // slot j / kBuckets, copy j % kBuckets
     uint32_t* s = st + kStatWords * j;
     s[0] = 0; s[1] = 0; s[2] = kNone; s[3] = kNone; s[4] = 0; s[5] = 0;
+    if (CONF) csum_of(a, b)[j] = 0;
   }
   if (tid == 0) {
     o[0] = n_true;
@@ -356,9 +373,10 @@ __global__ __launch_bounds__(kSelThreads) void k_cr_select(CrArgs a) {
 }
 
 // ---- 6. coordinate sums and bounding boxes of the kept regions ---------------------------------
+template <bool CONF>
 __global__ __launch_bounds__(kThreads) void k_cr_stats(CrArgs a) {
   __shared__ uint32_t slot[kTilePix];  // per tile-local key: 0 unused, 1 used, then slot + 2 or 1
-  __shared__ uint32_t acc[kStatWords][kTilePix];
+  __shared__ uint32_t acc[kStatWords + (CONF ? 1 : 0)][kTilePix];
   const int b = blockIdx.z, x0 = blockIdx.x * kTile, y0 = blockIdx.y * kTile;
   const uint32_t* parent = parent_of(a, b);
   const uint32_t* cnt = cnt_of(a, b);
@@ -368,6 +386,7 @@ __global__ __launch_bounds__(kThreads) void k_cr_stats(CrArgs a) {
     const int i = tid + k * kThreads;
     slot[i] = 0;
     acc[0][i] = 0; acc[1][i] = 0; acc[2][i] = kNone; acc[3][i] = kNone; acc[4][i] = 0; acc[5][i] = 0;
+    if (CONF) acc[kStatWords][i] = 0;
   }
   __syncthreads();
   // key of a pixel: its parent if that lies in this tile (its tile-local root, or for such a
@@ -406,8 +425,22 @@ __global__ __launch_bounds__(kThreads) void k_cr_stats(CrArgs a) {
     const int prev = __shfl_up(kk, 1, 64);  // by every lane, before any branch
     const bool head = lx == 0 || prev != kk;
     const unsigned long long heads = __ballot(head);
+    uint32_t csum = 0;
+    if (CONF) {
+      // the codes of a run, summed into its first lane: lane + off belongs to this lane's run
+      // when fewer than `rest` lanes separate them (rest: the lanes from this one to the end
+      // of its run; runs are contiguous inside a tile row)
+      const uint32_t rest = run_length((uint32_t)(heads >> (tid & 32)), lx);
+      if (kk >= 0) csum = a.conf[((size_t)b * a.H + y) * a.W + x];
+#pragma unroll
+      for (int off = 1; off < kTile; off <<= 1) {  // by every lane, before any branch
+        const uint32_t t = (uint32_t)__shfl_down((int)csum, off, 64);
+        if ((uint32_t)off < rest) csum += t;
+      }
+    }
     if (!head || kk < 0 || slot[kk] < 2) continue;
     const uint32_t n = run_length((uint32_t)(heads >> (tid & 32)), lx);
+    if (CONF) atomicAdd(&acc[kStatWords][kk], csum);
     atomicAdd(&acc[0][kk], n * (2 * x + n - 1) / 2); atomicAdd(&acc[1][kk], n * y);
     atomicMin(&acc[2][kk], x); atomicMin(&acc[3][kk], y);
     atomicMax(&acc[4][kk], x + n - 1); atomicMax(&acc[5][kk], y);
@@ -428,13 +461,18 @@ __global__ __launch_bounds__(kThreads) void k_cr_stats(CrArgs a) {
     if (acc[3][i] < s[3]) atomicMin(s + 3, acc[3][i]);
     if (acc[4][i] > s[4]) atomicMax(s + 4, acc[4][i]);
     if (acc[5][i] > s[5]) atomicMax(s + 5, acc[5][i]);
+    if (CONF)
+      atomicAdd(csum_of(a, b) + kBuckets * (slot[i] - 2) + (blockIdx.y * gridDim.x + blockIdx.x) % kBuckets,
+                acc[kStatWords][i]);
   }
 }
 
 // ---- 7. pack ---------------------------------------------------------------------------------
+template <bool CONF>
 __global__ __launch_bounds__(kMaxK) void k_cr_emit(CrArgs a) {
+  constexpr int RW = CONF ? 7 : 6;
   const int b = blockIdx.x, i = threadIdx.x;
-  uint32_t* o = a.out + (size_t)b * (4 + 6 * a.K);
+  uint32_t* o = a.out + (size_t)b * (4 + RW * a.K);
   const uint32_t n = o[0];
   if (i >= a.K || (uint32_t)i >= n) return;
   const uint32_t* s = stats_of(a, b) + kStatWords * kBuckets * i;
@@ -448,11 +486,18 @@ __global__ __launch_bounds__(kMaxK) void k_cr_emit(CrArgs a) {
     xh = s[4] > xh ? s[4] : xh;
     yh = s[5] > yh ? s[5] : yh;
   }
-  uint32_t* r = o + 4 + 6 * i;
+  uint32_t* r = o + 4 + RW * i;
   r[2] = sx;
   r[3] = sy;
   r[4] = xl | (yl << 16);
   r[5] = xh | (yh << 16);
+  if (CONF) {
+    const uint32_t* c = csum_of(a, b) + kBuckets * i;
+    uint32_t sc = 0;
+#pragma unroll
+    for (int q = 0; q < kBuckets; ++q) sc += c[q];
+    r[6] = sc;
+  }
 }
 
 }  // namespace
@@ -460,9 +505,9 @@ __global__ __launch_bounds__(kMaxK) void k_cr_emit(CrArgs a) {
 int class_regions_tile() { return kTile; }
 int class_regions_candidates() { return kCandidates; }
 
-size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w) {
+size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w, bool conf) {
   const size_t N = (size_t)crop_h * (size_t)crop_w;
-  return (size_t)B * frame_words(N) * sizeof(uint32_t);
+  return (size_t)B * (frame_words(N) + (conf ? (size_t)kMaxK * kBuckets : 0)) * sizeof(uint32_t);
 }
 
 void class_regions(const ClassRegionsParams& p, hipStream_t s) {
@@ -477,15 +522,23 @@ void class_regions(const ClassRegionsParams& p, hipStream_t s) {
   for (int i = 0; i < 8; ++i) a.cls[i] = p.classes[i];
   a.H = p.H; a.W = p.W; a.crop_h = p.crop_h; a.crop_w = p.crop_w; a.K = p.K; a.N = (int)N;
   a.min_pixels = (uint32_t)p.min_pixels;
+  a.conf = p.conf;
+  a.csum = p.conf ? p.ws + (size_t)p.B * frame_words((size_t)N) : nullptr;
   const dim3 tiles(cdiv(p.crop_w, kTile), cdiv(p.crop_h, kTile), p.B);
   hipLaunchKernelGGL(k_cr_local, tiles, dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(k_cr_merge, tiles, dim3(64), 0, s, a);
   const dim3 flat(cdiv(N, kThreads), p.B);
   hipLaunchKernelGGL(k_cr_count, flat, dim3(kThreads), 0, s, a);
   hipLaunchKernelGGL(k_cr_gather, flat, dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL(k_cr_select, dim3(p.B), dim3(kSelThreads), 0, s, a);
-  hipLaunchKernelGGL(k_cr_stats, tiles, dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL(k_cr_emit, dim3(p.B), dim3(kMaxK), 0, s, a);
+  if (p.conf) {
+    hipLaunchKernelGGL(k_cr_select<true>, dim3(p.B), dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_cr_stats<true>, tiles, dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(k_cr_emit<true>, dim3(p.B), dim3(kMaxK), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(k_cr_select<false>, dim3(p.B), dim3(kSelThreads), 0, s, a);
+    hipLaunchKernelGGL(k_cr_stats<false>, tiles, dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL(k_cr_emit<false>, dim3(p.B), dim3(kMaxK), 0, s, a);
+  }
   check_launch("class_regions");
 }
 

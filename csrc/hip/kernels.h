@@ -300,6 +300,10 @@ void matvec(const float* x, const float* w, const float* bias, float* out, int B
 // argmax), 5 the direct kernel (see model_ops.hip).
 void upsample_argmax(const bf16* logits, uint8_t* labels, int B, int h, int w, int K, int ldk,
                      int H, int W, hipStream_t s, int variant = 0);
+// The same labels and, in the same pass, conf[B, H, W] uint8 = floor(255 * p + 0.5) with p the
+// winning class's softmax probability over the K interpolated scores (1 <= K <= min(256, ldk)).
+void upsample_argmax_conf(const bf16* logits, uint8_t* labels, uint8_t* conf, int B, int h, int w,
+                          int K, int ldk, int H, int W, hipStream_t s);
 
 // ---- post-processing (postprocess.hip) -------------------------------------
 struct PostParams {
@@ -359,14 +363,17 @@ void yuv422_to_bgr(const uint8_t* src, uint8_t* dst, size_t n_macropixels, bool 
 // (label << 24) | root, pixels, sum_x, sum_y, x_min | y_min << 16, x_max | y_max << 16.
 // Words past those are not written. N < 2^24, N * max(crop_w, crop_h) < 2^32, 1 <= K <= 256,
 // N / min_pixels <= class_regions_candidates().
+// With `conf` (a [B, H, W] plane of per-pixel codes beside the labels) a record has a seventh
+// word, sum_conf: the exact sum of the codes of the region's pixels (out is [B, 4 + 7 K]).
 struct ClassRegionsParams {
   const uint8_t* labels = nullptr;  // [B, H, W] (row stride W)
   int B = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, K = 0, min_pixels = 0;
   uint32_t classes[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // bit c of the 256-bit set: class c is served
   uint32_t* out = nullptr;          // [B, 4 + 6 K]
-  uint32_t* ws = nullptr;           // class_regions_workspace_bytes(B, crop_h, crop_w)
+  uint32_t* ws = nullptr;           // class_regions_workspace_bytes(B, crop_h, crop_w, conf != nullptr)
+  const uint8_t* conf = nullptr;    // [B, H, W] or null
 };
-size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w);
+size_t class_regions_workspace_bytes(int B, int crop_h, int crop_w, bool conf = false);
 int class_regions_tile();        // tile edge of the tile-local pass
 int class_regions_candidates();  // most regions that may pass in one frame
 void class_regions(const ClassRegionsParams& p, hipStream_t s);

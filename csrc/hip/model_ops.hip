@@ -1202,4 +1202,137 @@ void upsample_argmax(const bf16* logits, uint8_t* labels, int B, int h, int w, i
   check_launch("upsample_argmax");
 }
 
+// ---------------------------------------------------------------- upsample + argmax + confidence
+// Label and confidence of every output pixel in one pass over the logits
+// (ops/reference_ops.py upsample_confidence is the definition): with u the bilinear
+// interpolant of the K real classes, label = first argmax_k u_k and
+// conf = floor(255 / sum_k exp(u_k - u_max) + 0.5), the rounded winning softmax probability.
+// exp(u_k - u_max) is one FMA + v_exp_f32: exp2(u_k * log2(e) - u_max * log2(e)). The rounding
+// of the subtrahend (at most 2^-24 relative of |u_max| log2(e)) scales every term of the sum
+// alike, the winner's included: below 2e-6 relative in the probability for |u| <= 32, 5e-4
+// of a code. No class is pruned: a lane-varying skip would cost a compare per class, about
+// what the quarter-rate exponential it saves costs.
+constexpr float kLog2e = 1.4426950408889634f;
+
+__device__ __forceinline__ uint8_t conf_code(float sum) {
+  // sum >= 1 (the winner's own term), so the code is at most 255
+  return (uint8_t)(int)(255.f * __builtin_amdgcn_rcpf(sum) + 0.5f);
+}
+
+// The interval form: Interval<KP, KC>::load as the label kernels, then per output pixel the
+// strict-compare first maximum of argmax_at<false> and the sum over the same NK values, which
+// stay in registers between the two. The end-point shortcut of emit() does not apply (the
+// sum needs every pixel). Labels and codes leave as per-lane byte stores, as variant 1.
+template <int KP, int KC>
+__global__ __launch_bounds__(256) void upsample_argmax_conf_interval_kernel(
+    const bf16* __restrict__ logits, uint8_t* __restrict__ labels, uint8_t* __restrict__ conf, int B,
+    int h, int w, int K, int ldk, int H, int W) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * H * w) return;
+  const int j = t % w;
+  const int Y = (t / w) % H;
+  const int b = t / (w * H);
+  Interval<KP, KC> iv;
+  iv.load(logits, b, Y, j, h, w, H, W, ldk);
+  constexpr int NK = Interval<KP, KC>::NK;
+  uint8_t* ol = labels + ((size_t)b * H + Y) * W;
+  uint8_t* oc = conf + ((size_t)b * H + Y) * W;
+  for (int X = iv.xs; X < iv.xe; ++X) {
+    const float lx1 = iv.lx(X);
+    float v[NK];
+    float best = -3.0e38f;
+    int arg = 0;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      v[k] = iv.v0[k] + lx1 * iv.dv[k];
+      if ((KC || k < K) && v[k] > best) { best = v[k]; arg = k; }
+    }
+    const float nb = -best * kLog2e;
+    float sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const float e = __builtin_amdgcn_exp2f(fmaf(v[k], kLog2e, nb));
+      sum += (KC || k < K) ? e : 0.f;
+    }
+    ol[X] = (uint8_t)arg;
+    oc[X] = conf_code(sum);
+  }
+}
+
+// The direct form (K > 32, ldk % 8 != 0, downsampling): one lane per output pixel, the four
+// source pixels gathered per class, twice (maximum, then sum) as K has no register bound.
+__global__ __launch_bounds__(256) void upsample_argmax_conf_kernel(const bf16* __restrict__ logits,
+                                                                   uint8_t* __restrict__ labels,
+                                                                   uint8_t* __restrict__ conf, int B,
+                                                                   int h, int w, int K, int ldk, int H,
+                                                                   int W) {
+  const long long total = (long long)B * H * W;
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int X = (int)(t % W);
+  const int Y = (int)((t / W) % H);
+  const int b = (int)(t / ((long long)W * H));
+  const float sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
+  const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+  const float fy = sh * (float)Y;
+  const int y0 = (int)fy;
+  const int yp = y0 < h - 1 ? 1 : 0;
+  const float ly1 = fy - (float)y0, ly0 = 1.f - ly1;
+  const float fx = sw * (float)X;
+  const int x0 = (int)fx;
+  const int xp = x0 < w - 1 ? 1 : 0;
+  const float lx1 = fx - (float)x0, lx0 = 1.f - lx1;
+  const bf16* p00 = logits + (((long long)b * h + y0) * w + x0) * ldk;
+  const bf16* p01 = p00 + xp * ldk;
+  const bf16* p10 = p00 + (long long)yp * w * ldk;
+  const bf16* p11 = p10 + xp * ldk;
+  float best = -3.0e38f;
+  int arg = 0;
+  for (int k = 0; k < K; ++k) {
+    const float v = ly0 * (lx0 * (float)p00[k] + lx1 * (float)p01[k]) +
+                    ly1 * (lx0 * (float)p10[k] + lx1 * (float)p11[k]);
+    if (v > best) { best = v; arg = k; }
+  }
+  const float nb = -best * kLog2e;
+  float sum = 0.f;
+  for (int k = 0; k < K; ++k) {
+    const float v = ly0 * (lx0 * (float)p00[k] + lx1 * (float)p01[k]) +
+                    ly1 * (lx0 * (float)p10[k] + lx1 * (float)p11[k]);
+    sum += __builtin_amdgcn_exp2f(fmaf(v, kLog2e, nb));
+  }
+  labels[t] = (uint8_t)arg;
+  conf[t] = conf_code(sum);
+}
+
+// The interval preconditions are upsample_argmax's; otherwise the direct kernel runs.
+void upsample_argmax_conf(const bf16* logits, uint8_t* labels, uint8_t* conf, int B, int h, int w,
+                          int K, int ldk, int H, int W, hipStream_t s) {
+  if (K < 1 || K > 256 || K > ldk) throw std::invalid_argument("upsample_argmax_conf: K outside 1 .. min(256, ldk)");
+  if (B < 1 || h < 1 || w < 1 || H < 1 || W < 1) throw std::invalid_argument("upsample_argmax_conf: bad shape");
+  const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
+  const int kp = K <= 24 ? 24 : 32;
+  const bool interval = K <= 32 && ldk % 8 == 0 && ldk >= kp && w >= 2 && W > 1 && sw > 0.f &&
+                        1.f / sw <= 30.f && (long long)B * H * w < (1LL << 31);
+  if (interval) {
+    const dim3 grid(cdiv((long long)B * H * w, 256));
+    if (K == 21)
+      hipLaunchKernelGGL((upsample_argmax_conf_interval_kernel<24, 21>), grid, dim3(256), 0, s, logits,
+                         labels, conf, B, h, w, K, ldk, H, W);
+    else if (K == 19)
+      hipLaunchKernelGGL((upsample_argmax_conf_interval_kernel<24, 19>), grid, dim3(256), 0, s, logits,
+                         labels, conf, B, h, w, K, ldk, H, W);
+    else if (K <= 24)
+      hipLaunchKernelGGL((upsample_argmax_conf_interval_kernel<24, 0>), grid, dim3(256), 0, s, logits,
+                         labels, conf, B, h, w, K, ldk, H, W);
+    else
+      hipLaunchKernelGGL((upsample_argmax_conf_interval_kernel<32, 0>), grid, dim3(256), 0, s, logits,
+                         labels, conf, B, h, w, K, ldk, H, W);
+    check_launch("upsample_argmax_conf interval");
+    return;
+  }
+  hipLaunchKernelGGL(upsample_argmax_conf_kernel, dim3(cdiv((long long)B * H * W, 256)), dim3(256), 0, s,
+                     logits, labels, conf, B, h, w, K, ldk, H, W);
+  check_launch("upsample_argmax_conf");
+}
+
 }  // namespace ssa

@@ -164,6 +164,8 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "y_min", 8, F.TYPE_FLOAT)
     _field(m, "x_max", 9, F.TYPE_FLOAT)
     _field(m, "y_max", 10, F.TYPE_FLOAT)
+    # mean winning-class softmax probability of the region's pixels (--serve_confidence; else 0)
+    _field(m, "confidence", 11, F.TYPE_FLOAT)
 
     # the regions of the stream's latest frame, by (pixels descending, first pixel ascending)
     m = fd.message_type.add(); m.name = "ClassRegions"
@@ -177,6 +179,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "regions", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, ".sem_seg_server.v2.ClassRegion")
     _field(m, "total_regions", 9, F.TYPE_UINT32)  # regions that passed; more than stored: truncated
     _field(m, "truncated", 10, F.TYPE_BOOL)
+    _field(m, "has_confidence", 11, F.TYPE_BOOL)  # the regions carry a confidence
 
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"

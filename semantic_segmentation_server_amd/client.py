@@ -107,7 +107,8 @@ def print_regions(m) -> None:
     for r in m.regions:
         print("  {:>3} {:<20} {:>8} px  area {:.4f}  centre ({:.3f}, {:.3f})  box ({:.3f}, {:.3f}) - "
               "({:.3f}, {:.3f})".format(r.class_id, r.label, r.pixels, r.area, r.cx, r.cy, r.x_min,
-                                       r.y_min, r.x_max, r.y_max))
+                                       r.y_min, r.x_max, r.y_max) +
+              ("  conf {:.3f}".format(r.confidence) if m.has_confidence else ""))
 
 
 def main(argv=None) -> int:

@@ -67,6 +67,7 @@ class Config:
     max_regions: int = 64                  # region records per frame (1 .. 256), largest first
     region_min_area_ratio: float = 0.002   # smallest region served, as a share of input_size^2
     region_classes: Optional[str] = None   # comma list of class ids / label names; None: all but 0
+    serve_confidence: bool = False         # per-pixel confidence on the device, served per class region
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -88,6 +89,9 @@ class Config:
         if self.pixel_format not in PIXEL_FORMATS:
             raise ValueError(f"--pixel_format must be one of {', '.join(PIXEL_FORMATS)}, "
                              f"got {self.pixel_format!r}")
+        if self.serve_confidence and not self.serve_regions:
+            raise ValueError("--serve_confidence requires --serve_regions: the confidence is served "
+                             "per class region (v2 GetClassRegions)")
         if self.pixel_format != "bgr":
             if self.camera_width % 2:
                 raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
@@ -176,6 +180,10 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--region_classes", default=d.region_classes,
                    help="comma list of class ids or label names whose regions are served "
                         "(default: every class but 0)")
+    p.add_argument("--serve_confidence", action="store_true",
+                   help="compute the winning class's softmax probability of every pixel on the "
+                        "device and serve its mean per class region (v2 GetClassRegions "
+                        "confidence); requires --serve_regions")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

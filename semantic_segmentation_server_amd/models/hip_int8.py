@@ -52,7 +52,8 @@ class HipDeepLabInt8(HipPlanModel):
 
     def __init__(self, model: DeepLabV3, device: torch.device, cfg=None,
                  scales: Optional[Dict[str, float]] = None, calib_hw: int = 257):
-        super().__init__(model, device, cfg.input_size if cfg is not None else 1025)
+        super().__init__(model, device, cfg.input_size if cfg is not None else 1025,
+                         confidence=bool(getattr(cfg, "serve_confidence", False)))
         if scales is None:
             x = synthetic_normalized(4, calib_hw, calib_hw, torch.Generator().manual_seed(11))
             m32 = model.float()
@@ -154,10 +155,7 @@ class HipDeepLabInt8(HipPlanModel):
         ops.append(I8(
             next(step), proj, lw8, lsc, lb, logits, B=B, IH=h, IW=w, Cin=A, OH=h, OW=w,
             Cout=self.num_classes, ldo=self.ldk, act=None))
-        labels = buf("labels", B, H, W, dtype=torch.uint8)
-        ops.append(lambda *_, h=h, w=w: K.upsample_argmax(
-            logits, self._labels_out if self._labels_out is not None else labels, B=B, h=h, w=w,
-            K=self.num_classes, ldk=self.ldk, H=H, W=W, variant=K.UPSAMPLE_VARIANTS["lane"]))
+        ops += self._final_op(buf, logits, B, h, w, ("lane",))
         return ops
 
     def _aspp_branches(self, bufs, x, cat, B, h, w, c):

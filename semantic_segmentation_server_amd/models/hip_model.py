@@ -130,7 +130,8 @@ def _rows_per_band(work: int, OH: int, targets) -> List[int]:
 
 class HipDeepLab(HipPlanModel):
     def __init__(self, model: DeepLabV3, device: torch.device, cfg=None):
-        super().__init__(model, device, cfg.input_size if cfg is not None else 513)
+        super().__init__(model, device, cfg.input_size if cfg is not None else 513,
+                         confidence=bool(getattr(cfg, "serve_confidence", False)))
         dev = device
         bb = model.backbone
         self.kind = "mnv2" if isinstance(bb, MobileNetV2Backbone) else "resnet50"
@@ -449,14 +450,9 @@ class HipDeepLab(HipPlanModel):
         return [Choice("aspp.head", head + [("split", split)])], logits
 
     def _upsample(self, B, buf, logits, h, w):
-        H, W = self.H, self.W
-        labels = buf("labels", B, H, W, dtype=torch.uint8)
         # upsample + argmax: row-block (LDS-staged, coalesced stores), per-lane stores, or
-        # per-lane with wave-union class pruning
-        return [Choice("upsample", [(name, [lambda *_, v=K.UPSAMPLE_VARIANTS[name]: K.upsample_argmax(
-            logits, self._labels_out if self._labels_out is not None else labels, B=B, h=h, w=w,
-            K=self.num_classes, ldk=self.ldk, H=H, W=W, variant=v)])
-            for name in ("rows", "lane", "union", "cand")])]
+        # per-lane with wave-union class pruning; with confidence, the one two-plane kernel
+        return self._final_op(buf, logits, B, h, w, ("rows", "lane", "union", "cand"))
 
     # ------------------------------------------------------- MobileNetV2 block
     def _mnv2_block(self, buf, i, blk, B, x, h, w, c):

@@ -107,13 +107,17 @@ class HipPlanModel:
     A subclass packs its weights, sets ``kind`` (the tune-file key prefix) and implements
     ``_build(B, Hc, Wc, buf, bufs) -> ops``. ``buf(name, *shape, dtype=buf_dtype)`` allocates
     a zeroed plan buffer into ``bufs``, "logits" and "labels" among them; the last op writes
-    ``self._labels_out if self._labels_out is not None else labels``."""
+    ``self._labels_out if self._labels_out is not None else labels``. With ``confidence`` the
+    plan also has a "conf" buffer (uint8 [B, H, W] codes, ``reference_ops.upsample_confidence``)
+    and its last op writes both planes (``_final_op``)."""
 
     kind = ""
     buf_dtype = torch.bfloat16
 
-    def __init__(self, model, device: torch.device, input_size: int):
+    def __init__(self, model, device: torch.device, input_size: int, confidence: bool = False):
         self.device = device
+        self.confidence = bool(confidence)
+        self._conf_out: Optional[torch.Tensor] = None  # segment(conf_out=): caller's conf plane
         self.model = model
         self.H = self.W = int(input_size)
         self.num_classes = model.num_classes
@@ -167,6 +171,23 @@ class HipPlanModel:
             bufs[name] = t
             return t
         return buf
+
+    def _final_op(self, buf, logits, B, h, w, variants):
+        """The plan's last step: ``upsample_argmax`` as the "upsample" choice over ``variants``,
+        or with ``confidence`` one plain op that writes the labels and the "conf" buffer."""
+        from ..ops import hip_ops as K
+        H, W = self.H, self.W
+        labels = buf("labels", B, H, W, dtype=torch.uint8)
+        if self.confidence:
+            conf = buf("conf", B, H, W, dtype=torch.uint8)
+            return [lambda *_: K.upsample_argmax_conf(
+                logits, self._labels_out if self._labels_out is not None else labels,
+                self._conf_out if self._conf_out is not None else conf, B=B, h=h, w=w,
+                K=self.num_classes, ldk=self.ldk, H=H, W=W)]
+        ups = [(name, [lambda *_, v=K.UPSAMPLE_VARIANTS[name]: K.upsample_argmax(
+            logits, self._labels_out if self._labels_out is not None else labels, B=B, h=h, w=w,
+            K=self.num_classes, ldk=self.ldk, H=H, W=W, variant=v)]) for name in variants]
+        return [Choice("upsample", ups)] if len(ups) > 1 else ups[0][1]
 
     @staticmethod
     def _launch(ops: List[Callable], args) -> None:
@@ -275,10 +296,12 @@ class HipPlanModel:
 
     # ------------------------------------------------------------------ run
     def segment(self, frames: torch.Tensor, lut_x: torch.Tensor, lut_y: torch.Tensor,
-                out: Optional[torch.Tensor] = None, part: int = 0) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, part: int = 0,
+                conf_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """frames: (B, Hc, Wc, 3) uint8 BGR on device -> (B, H, W) uint8 labels (static
         buffer, or ``out``). ``part``: which independent copy of the plan to run (the
-        engine's concurrent half-batches use parts 0 and 1)."""
+        engine's concurrent half-batches use parts 0 and 1). A model built with ``confidence``
+        also writes the confidence plane, into the plan's "conf" buffer or ``conf_out``."""
         B, Hc, Wc, _ = frames.shape
         if lut_x.numel() != self.W or lut_y.numel() != self.H:
             raise ValueError("letterbox LUTs do not match the model input size")
@@ -286,13 +309,19 @@ class HipPlanModel:
         if out is not None and (out.shape != bufs["labels"].shape or out.dtype != torch.uint8
                                 or not out.is_contiguous() or out.device != bufs["labels"].device):
             raise ValueError("segment: out must match the (B, H, W) uint8 label buffer")
+        if conf_out is not None:
+            if not self.confidence:
+                raise ValueError("segment: conf_out needs a model built with confidence")
+            if (conf_out.shape != bufs["conf"].shape or conf_out.dtype != torch.uint8
+                    or not conf_out.is_contiguous() or conf_out.device != bufs["conf"].device):
+                raise ValueError("segment: conf_out must match the (B, H, W) uint8 conf buffer")
         frames = frames.contiguous()
-        self._labels_out = out
+        self._labels_out, self._conf_out = out, conf_out
         try:
             for op in ops:
                 op(frames, lut_x, lut_y)
         finally:
-            self._labels_out = None
+            self._labels_out = self._conf_out = None
         return bufs["labels"] if out is None else out
 
     def logits(self, frames, lut_x, lut_y) -> torch.Tensor:

@@ -1147,6 +1147,34 @@ def upsample_argmax(logits, labels, *, B, h, w, K, ldk, H, W, variant: int = 0):
     return labels
 
 
+def upsample_argmax_conf(logits, labels, conf, *, B, h, w, K, ldk, H, W):
+    """``upsample_argmax`` plus the per-pixel confidence, in one pass over the logits
+    (csrc/hip/model_ops.hip; the definition is ``reference_ops.upsample_confidence``):
+    ``labels`` and ``conf`` are contiguous uint8 [B, H, W] planes on the logits' device,
+    ``conf = floor(255 * p + 0.5)`` with p the winning class's softmax probability over the K
+    interpolated scores. Everything is checked before anything is launched."""
+    _chk(logits, torch.bfloat16, "logits", B * h * w * ldk)
+    for name, t in (("labels", labels), ("conf", conf)):
+        _chk(t, torch.uint8, name)
+        if tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {H}, {W})")
+        if t.device != logits.device:
+            raise ValueError(f"upsample_argmax_conf: logits and {name} are on different devices")
+    if min(B, h, w, H, W) < 1:
+        raise ValueError(f"upsample_argmax_conf: bad shape B {B}, {h} x {w} -> {H} x {W}")
+    if not 1 <= K <= 256:
+        raise ValueError(f"upsample_argmax_conf: K {K} outside 1 .. 256")
+    if K > ldk:
+        raise ValueError("K > ldk")
+    lo, hi = sorted((labels.data_ptr(), conf.data_ptr()))
+    if lo + B * H * W > hi:
+        raise ValueError("upsample_argmax_conf: labels and conf overlap")
+    _hip_mod().upsample_argmax_conf(_ptr(logits), _ptr(labels), _ptr(conf), B, h, w, K, ldk, H, W,
+                                    _stream())
+    _dbg('upsample_argmax_conf')
+    return labels, conf
+
+
 def post_workspace_bytes(B, H, W, K, bins) -> int:
     return int(_hip_mod().post_workspace_bytes(B, H, W, K, bins))
 
@@ -1248,19 +1276,31 @@ REGION_CANDIDATES = 4096            # most regions that may pass in one frame (t
 REGION_MAX_K = 256
 
 
-def class_regions_workspace_bytes(B, crop_h, crop_w) -> int:
-    return int(_hip_mod().class_regions_workspace_bytes(B, crop_h, crop_w))
+def class_regions_workspace_bytes(B, crop_h, crop_w, conf: bool = False) -> int:
+    if not conf:
+        return int(_hip_mod().class_regions_workspace_bytes(B, crop_h, crop_w))
+    return int(_hip_mod().class_regions_workspace_bytes(B, crop_h, crop_w, True))
 
 
-def class_regions(labels, out, ws, *, B, H, W, crop_h, crop_w, classes, min_pixels, K):
+def class_regions(labels, out, ws, *, B, H, W, crop_h, crop_w, classes, min_pixels, K, conf=None):
     """Class regions of ``labels[:, :crop_h, :crop_w]`` (csrc/hip/class_regions.hip; the format
     is postprocess/regions.py's): per frame ``out[b] = [n_regions, N, crop_w, crop_h, 6 words
     per region ...]`` with the first ``min(n_regions, K)`` regions of at least ``min_pixels``
     pixels by (pixels descending, root ascending). ``classes``: the served set (class ids or a
     256-bit int mask). ``out``: uint32/int32 [B, 4 + 6 K]; ``ws``: at least
-    ``class_regions_workspace_bytes``."""
+    ``class_regions_workspace_bytes``. With ``conf`` (a uint8 [B, H, W] plane of per-pixel
+    confidence codes) a region has a seventh word, ``sum_conf``: ``out`` is [B, 4 + 7 K] and
+    ``ws`` at least ``class_regions_workspace_bytes(..., conf=True)``."""
     from ..postprocess import regions as RG
     _chk(labels, torch.uint8, "labels", B * H * W)
+    rw = 6
+    if conf is not None:
+        rw = 7
+        _chk(conf, torch.uint8, "conf")
+        if tuple(conf.shape) != (B, H, W):
+            raise ValueError(f"conf: shape {tuple(conf.shape)} != ({B}, {H}, {W})")
+        if conf.device != labels.device:
+            raise ValueError("class_regions: labels and conf are on different devices")
     if out.dtype not in (torch.int32, torch.uint32):
         raise TypeError(f"out: expected uint32 or int32, got {out.dtype}")
     _chk(out, out.dtype, "out")
@@ -1269,18 +1309,18 @@ def class_regions(labels, out, ws, *, B, H, W, crop_h, crop_w, classes, min_pixe
     if not (1 <= crop_h <= H and 1 <= crop_w <= W):
         raise ValueError(f"class_regions: crop {crop_h} x {crop_w} outside the {H} x {W} map")
     RG.check_geometry(crop_w, crop_h, min_pixels, K)
-    if tuple(out.shape) != (B, 4 + 6 * K):
-        raise ValueError(f"out: shape {tuple(out.shape)} != ({B}, {4 + 6 * K})")
+    if tuple(out.shape) != (B, 4 + rw * K):
+        raise ValueError(f"out: shape {tuple(out.shape)} != ({B}, {4 + rw * K})")
     mask = RG.class_mask(classes)
     m = _hip_mod()
     if (m.REGION_TILE != REGION_TILE_W or m.REGION_CANDIDATES != REGION_CANDIDATES
             or RG.REGION_CANDIDATES != REGION_CANDIDATES or RG.MAX_REGIONS != REGION_MAX_K):
         raise RuntimeError("class_regions: REGION_TILE / REGION_CANDIDATES differ from the built module's")
-    _chk(ws, torch.uint8, "ws", class_regions_workspace_bytes(B, crop_h, crop_w))
+    _chk(ws, torch.uint8, "ws", class_regions_workspace_bytes(B, crop_h, crop_w, conf is not None))
     w64 = (1 << 64) - 1
     m.class_regions(_ptr(labels), B, H, W, crop_h, crop_w, mask & w64, (mask >> 64) & w64,
                     (mask >> 128) & w64, (mask >> 192) & w64, int(min_pixels), int(K), _ptr(out),
-                    _ptr(ws), _stream())
+                    _ptr(ws), _stream(), _ptr(conf))
     _dbg('class_regions')
     return out
 

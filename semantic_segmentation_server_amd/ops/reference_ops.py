@@ -98,6 +98,21 @@ def upsample_argmax(logits: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return up.argmax(1).to(torch.uint8)
 
 
+def upsample_confidence(logits: torch.Tensor, H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(N, K, h, w) logits -> ((N, H, W) uint8 labels, (N, H, W) uint8 confidence codes).
+
+    The definition of the served confidence: with ``u`` the bilinear ``align_corners=True``
+    upsample of the K real classes (as ``upsample_argmax``), ``label = argmax_k u`` (first
+    max) and ``p = max_k softmax(u) = 1 / sum_k exp(u_k - u_max)``, the winning class's
+    probability; ``conf = floor(255 * p + 0.5)``. ``p >= 1 / K``, so K = 21 gives codes
+    12 .. 255. Oracle of ``hip_ops.upsample_argmax_conf`` and the CPU / torch path."""
+    up = F.interpolate(logits.float(), size=(H, W), mode="bilinear", align_corners=True)
+    labels = up.argmax(1)
+    p = 1.0 / torch.exp(up - up.amax(1, keepdim=True)).sum(1)
+    conf = torch.floor(255.0 * p + 0.5).clamp_(0, 255).to(torch.uint8)
+    return labels.to(torch.uint8), conf
+
+
 def decisive_agreement(got: torch.Tensor, ref: torch.Tensor, k: float = 4.0) -> Tuple[float, float]:
     """Argmax agreement of ``got`` with ``ref`` (both (N, K, h, w) logits) on the pixels
     whose ``ref`` decision is not a near-tie at the measured error: top-1 minus top-2

@@ -184,6 +184,9 @@ class DataParallelPipeline:
         # --serve_regions: the same for each step's class-region words ([B, 4 + 6 K], about
         # 1.5 KiB per frame: a plain async copy)
         self.region_cap = int(getattr(engine, "region_cap", 0) or 0)
+        # --serve_confidence: 7 words a region (sum_conf); the hub is told so with every push
+        self.region_words = int(getattr(engine, "region_words", 6) or 6)
+        self._region_kw = {"conf": True} if self.region_words == 7 else {}
         if self.region_cap and ctx.initialized and ctx.world > 1:
             raise ValueError("serve_regions is not supported in a multi-rank group (world size "
                              f"{ctx.world}): class regions are not gathered across ranks; run one "
@@ -270,7 +273,7 @@ class DataParallelPipeline:
         self.local_mask = [torch.zeros((self.B, 4 + self.mask_cap), dtype=torch.int32,
                                        pin_memory=self.cuda) for _ in range(NS)] \
             if self.mask_cap else None
-        self.local_regions = [torch.zeros((self.B, 4 + 6 * self.region_cap), dtype=torch.int32,
+        self.local_regions = [torch.zeros((self.B, 4 + self.region_words * self.region_cap), dtype=torch.int32,
                                           pin_memory=self.cuda) for _ in range(NS)] \
             if self.region_cap else None
         if gather == "host" and ctx.initialized:
@@ -495,7 +498,8 @@ class DataParallelPipeline:
             if self.mask_cap and self.hub is not None and hasattr(self.hub, "push_masks"):
                 self.hub.push_masks(self.engine.host_masks(labels), self._node_meta(fids, strm, tss))
             if self.region_cap and self.hub is not None and hasattr(self.hub, "push_regions"):
-                self.hub.push_regions(self.engine.host_regions(labels), self._node_meta(fids, strm, tss))
+                self.hub.push_regions(self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None)),
+                                      self._node_meta(fids, strm, tss), **self._region_kw)
             return self.engine.records_from_labels(labels, fids, tss, strm)
         # the run words of this step's label maps: produced with the records (same graph,
         # same stream), copied with them, before the step's event
@@ -766,4 +770,4 @@ class DataParallelPipeline:
         if self.mask_cap and hasattr(self.hub, "push_masks"):
             self.hub.push_masks(self.local_mask[slot].numpy(), meta)
         if self.region_cap and hasattr(self.hub, "push_regions"):
-            self.hub.push_regions(self.local_regions[slot].numpy(), meta)
+            self.hub.push_regions(self.local_regions[slot].numpy(), meta, **self._region_kw)

@@ -20,8 +20,12 @@ from ..runtime.results import RECORD_DTYPE
 class DevicePostprocess:
     def __init__(self, device: torch.device, H: int, W: int, palette: np.ndarray, K: int = 64,
                  bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
-                 region_classes: int = 0, region_min_pixels: int = 1):
+                 region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False):
         self.device = device
+        # region_conf (--serve_confidence): run() takes the confidence plane beside the labels
+        # and the region records have 7 words (sum_conf)
+        self.region_conf = bool(region_conf)
+        self.region_words = 7 if self.region_conf else 6
         # records per frame of the class-region kernels (class_regions.hip); 0: no kernel, no
         # buffer, no launch. region_classes: the served 256-bit class set
         self.region_cap = int(region_cap)
@@ -77,20 +81,21 @@ class DevicePostprocess:
     def region_buffers(self, B: int, crop_w: int, crop_h: int):
         """(workspace, [B, 4 + 6 region_cap] int32 region words) of the class-region kernels for
         a batch of B frames: static and shared like ``mask_buffers``. The kernels of every run
-        initialise what they read of the workspace."""
+        initialise what they read of the workspace. With ``region_conf``: 7 words a region."""
         key = (B, crop_w, crop_h)
         if key not in self._region_bufs:
             from . import regions as RG
             RG.check_geometry(crop_w, crop_h, self.region_min_pixels, self.region_cap)
-            ws = torch.zeros(hip_ops.class_regions_workspace_bytes(B, crop_h, crop_w),
+            ws = torch.zeros(hip_ops.class_regions_workspace_bytes(B, crop_h, crop_w, self.region_conf),
                              dtype=torch.uint8, device=self.device)
-            words = torch.zeros((B, 4 + 6 * self.region_cap), dtype=torch.int32, device=self.device)
+            words = torch.zeros((B, 4 + self.region_words * self.region_cap), dtype=torch.int32,
+                                device=self.device)
             self._region_bufs[key] = (ws, words)
         return self._region_bufs[key]
 
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
             out: torch.Tensor = None, mask_out: torch.Tensor = None,
-            region_out: torch.Tensor = None) -> torch.Tensor:
+            region_out: torch.Tensor = None, conf: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
         shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
@@ -98,7 +103,9 @@ class DevicePostprocess:
         same captured graph), into ``mask_buffers(B)`` or ``mask_out`` ([B, 4 + mask_cap]
         int32 rows); ``last_mask`` is the buffer written. With ``region_cap`` the class regions
         follow on the same stream, into ``region_buffers(B)`` or ``region_out`` ([B, 4 + 6
-        region_cap] int32 rows); ``last_regions`` is the buffer written."""
+        region_cap] int32 rows); ``last_regions`` is the buffer written. With ``region_conf``,
+        ``conf`` is the [B, H, W] uint8 confidence plane of ``labels`` and the rows are [B, 4 + 7
+        region_cap]."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -122,9 +129,12 @@ class DevicePostprocess:
             rws, words = self.region_buffers(B, crop_w, crop_h)
             if region_out is not None:
                 words = region_out
+            if self.region_conf and conf is None:
+                raise ValueError("DevicePostprocess.run: region_conf needs the conf plane")
             hip_ops.class_regions(labels, words, rws, B=B, H=self.H, W=self.W, crop_h=crop_h,
                                   crop_w=crop_w, classes=self.region_classes,
-                                  min_pixels=self.region_min_pixels, K=self.region_cap)
+                                  min_pixels=self.region_min_pixels, K=self.region_cap,
+                                  conf=conf if self.region_conf else None)
             self.last_regions = words
         return rec
 

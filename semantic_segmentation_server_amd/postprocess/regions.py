@@ -26,6 +26,12 @@ descending, then ``root`` ascending. Per frame, on the device and on the host,
 
 Words past the used ones are not written.
 
+With a per-pixel confidence plane (uint8 codes beside the labels, ``--serve_confidence``) a
+region has a seventh word, ``6  sum_conf``: the exact integer sum of the codes of its pixels
+(``pixels < 2^24`` and codes ``<= 255``, so it fits 32 bits), and a frame is
+``uint32[4 + 7 * K]`` with the same header. The mean confidence of a region is
+``sum_conf / (255 * pixels)``.
+
 This module is the oracle of the device kernels (``csrc/hip/class_regions.hip``), the encoder
 of the CPU / torch / exact paths, and the decoder of the RPC.
 """
@@ -37,6 +43,7 @@ import numpy as np
 
 HEADER = 4
 WORDS = 6                      # per region
+WORDS_CONF = 7                 # per region with sum_conf
 MAX_PIXELS = 1 << 24           # a root is stored in 24 bits
 MAX_REGIONS = 256              # K
 REGION_CANDIDATES = 4096       # most regions that may pass in a frame (the kernel file's constant)
@@ -44,7 +51,11 @@ REGION_CANDIDATES = 4096       # most regions that may pass in a frame (the kern
 REGION_DTYPE = np.dtype([("label", np.uint8), ("root", np.uint32), ("pixels", np.uint32),
                          ("sum_x", np.uint32), ("sum_y", np.uint32),
                          ("x_min", np.uint16), ("y_min", np.uint16),
-                         ("x_max", np.uint16), ("y_max", np.uint16)])
+                         ("x_max", np.uint16), ("y_max", np.uint16), ("sum_conf", np.uint32)])
+
+
+def words_per_region(conf: bool = False) -> int:
+    return WORDS_CONF if conf else WORDS
 
 Classes = Union[int, Iterable[int]]
 
@@ -131,8 +142,9 @@ def label_components(labels: np.ndarray, mask: int) -> np.ndarray:
 
 
 def region_table(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes,
-                 min_pixels: int = 1) -> np.ndarray:
-    """REGION_DTYPE[n]: every passing region of the crop, in the output order."""
+                 min_pixels: int = 1, conf: Optional[np.ndarray] = None) -> np.ndarray:
+    """REGION_DTYPE[n]: every passing region of the crop, in the output order. ``sum_conf``
+    is summed from ``conf`` (a uint8 map beside ``labels``) and 0 without it."""
     lab = np.ascontiguousarray(np.asarray(labels)[:crop_h, :crop_w])
     roots = label_components(lab, class_mask(classes)).reshape(-1)
     on = np.flatnonzero(roots >= 0)
@@ -153,13 +165,18 @@ def region_table(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes,
     tab["sum_x"], tab["sum_y"] = np.add.reduceat(x, first), np.add.reduceat(y, first)
     tab["x_min"], tab["y_min"] = np.minimum.reduceat(x, first), np.minimum.reduceat(y, first)
     tab["x_max"], tab["y_max"] = np.maximum.reduceat(x, first), np.maximum.reduceat(y, first)
+    if conf is not None:
+        c = np.ascontiguousarray(np.asarray(conf)[:crop_h, :crop_w]).reshape(-1).astype(np.int64)
+        tab["sum_conf"] = np.add.reduceat(c[on], first)
     tab = tab[keep]
     return tab[np.lexsort((tab["root"], -tab["pixels"].astype(np.int64)))]
 
 
-def pack(tab: np.ndarray) -> np.ndarray:
-    """REGION_DTYPE[n] -> uint32[n, 6] record words."""
-    w = np.zeros((len(tab), WORDS), np.uint32)
+def pack(tab: np.ndarray, conf: bool = False) -> np.ndarray:
+    """REGION_DTYPE[n] -> uint32[n, 6] record words ([n, 7] with ``conf``)."""
+    w = np.zeros((len(tab), words_per_region(conf)), np.uint32)
+    if conf:
+        w[:, 6] = tab["sum_conf"]
     w[:, 0] = (tab["label"].astype(np.uint32) << 24) | tab["root"]
     w[:, 1], w[:, 2], w[:, 3] = tab["pixels"], tab["sum_x"], tab["sum_y"]
     w[:, 4] = tab["x_min"].astype(np.uint32) | (tab["y_min"].astype(np.uint32) << 16)
@@ -168,9 +185,10 @@ def pack(tab: np.ndarray) -> np.ndarray:
 
 
 def encode(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes, min_pixels: int,
-           K: int, out: Optional[np.ndarray] = None) -> np.ndarray:
-    """``labels[H, W]`` uint8 -> ``uint32[4 + 6 K]``. Unwritten words keep ``out``'s values
-    (zero without ``out``)."""
+           K: int, out: Optional[np.ndarray] = None, conf: Optional[np.ndarray] = None) -> np.ndarray:
+    """``labels[H, W]`` uint8 -> ``uint32[4 + 6 K]``; with ``conf[H, W]`` uint8, the
+    7-word records: ``uint32[4 + 7 K]``. Unwritten words keep ``out``'s values (zero without
+    ``out``)."""
     labels = np.asarray(labels)
     if labels.ndim != 2 or labels.dtype != np.uint8:
         raise ValueError("regions.encode: labels must be a 2-D uint8 map")
@@ -178,26 +196,35 @@ def encode(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes, min_p
     if crop_h > labels.shape[0] or crop_w > labels.shape[1]:
         raise ValueError(f"regions.encode: crop {crop_h} x {crop_w} outside the "
                          f"{labels.shape[0]} x {labels.shape[1]} map")
+    rw = words_per_region(conf is not None)
+    if conf is not None:
+        conf = np.asarray(conf)
+        if conf.shape != labels.shape or conf.dtype != np.uint8:
+            raise ValueError("regions.encode: conf must be a uint8 map of the labels' shape")
     if out is None:
-        out = np.zeros(HEADER + WORDS * K, np.uint32)
-    elif out.shape != (HEADER + WORDS * K,) or out.dtype != np.uint32:
-        raise ValueError("regions.encode: out must be uint32[4 + 6 K]")
-    tab = region_table(labels, crop_w, crop_h, classes, min_pixels)
+        out = np.zeros(HEADER + rw * K, np.uint32)
+    elif out.shape != (HEADER + rw * K,) or out.dtype != np.uint32:
+        raise ValueError(f"regions.encode: out must be uint32[4 + {rw} K]")
+    tab = region_table(labels, crop_w, crop_h, classes, min_pixels, conf)
     k = min(len(tab), K)
     out[0], out[1], out[2], out[3] = len(tab), crop_w * crop_h, crop_w, crop_h
-    out[HEADER:HEADER + WORDS * k] = pack(tab[:k]).reshape(-1)
+    out[HEADER:HEADER + rw * k] = pack(tab[:k], conf is not None).reshape(-1)
     return out
 
 
-def used_words(words: np.ndarray, K: Optional[int] = None) -> int:
-    """Header + stored records: ``4 + 6 * min(n_regions, K)`` (``K`` defaults to the array's)."""
-    K = (len(words) - HEADER) // WORDS if K is None else K
-    return HEADER + WORDS * min(int(words[0]), K)
+def used_words(words: np.ndarray, K: Optional[int] = None, conf: bool = False) -> int:
+    """Header + stored records: ``4 + 6 * min(n_regions, K)`` (``K`` defaults to the array's);
+    7-word records with ``conf``."""
+    rw = words_per_region(conf)
+    K = (len(words) - HEADER) // rw if K is None else K
+    return HEADER + rw * min(int(words[0]), K)
 
 
-def decode(words: np.ndarray) -> np.ndarray:
+def decode(words: np.ndarray, conf: bool = False) -> np.ndarray:
     """``uint32[>= 4 + 6 * stored]`` -> REGION_DTYPE[stored], the stored regions in order
-    (``stored = min(n_regions, slots of the array)``; ``words[0]`` is the true total)."""
+    (``stored = min(n_regions, slots of the array)``; ``words[0]`` is the true total). With
+    ``conf`` the records have 7 words; without, ``sum_conf`` is 0."""
+    WORDS = words_per_region(conf)
     words = np.asarray(words)
     if words.ndim != 1 or len(words) < HEADER:
         raise ValueError("regions: words must be a 1-D array with the 4 header words")
@@ -212,4 +239,6 @@ def decode(words: np.ndarray) -> np.ndarray:
     tab["pixels"], tab["sum_x"], tab["sum_y"] = w[:, 1], w[:, 2], w[:, 3]
     tab["x_min"], tab["y_min"] = w[:, 4] & np.uint32(0xFFFF), w[:, 4] >> np.uint32(16)
     tab["x_max"], tab["y_max"] = w[:, 5] & np.uint32(0xFFFF), w[:, 5] >> np.uint32(16)
+    if conf:
+        tab["sum_conf"] = w[:, 6]
     return tab

@@ -1,7 +1,9 @@
 """Captured steps of the engine, one class per capture form: the hipGraphs of one frame buffer
 and the static outputs they write (``labels``; ``post``: packed records or None; ``mask``:
---serve_masks run words or None; ``regions``: --serve_regions region words or None). ``replay()`` issues that form's replays, waits and event
-records; after ``consumed`` the buffer may be refilled (None: the model ran on the caller's stream).
+--serve_masks run words or None; ``regions``: --serve_regions region words or None; ``conf``: the
+--serve_confidence plane of ``labels``, which the post-processing graph reads, or None).
+``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
+may be refilled (None: the model ran on the caller's stream).
 
 With a raw pixel format (``eng.frame_channels == 2``) the frame buffer holds packed 4:2:2 bytes
 and every step owns ``bgr``, the BGR frames its model reads: the conversion is the first kernel
@@ -47,7 +49,8 @@ class WholeStep:
     def __init__(self, eng, frames):
         self.frames, self.consumed = frames, None
         self.bgr = bgr = eng.bgr_buffer(frames)
-        self.graph, (self.labels, self.post, self.mask, self.regions) = _graph(lambda: eng._step_outputs(frames, bgr))
+        self.graph, (self.labels, self.post, self.mask, self.regions, self.conf) = _graph(
+            lambda: eng._step_all(frames, bgr))
 
     def replay(self) -> None:
         self.graph.replay()
@@ -63,9 +66,18 @@ class SplitStep:
         # the model writes the step's own label maps
         self.labels = lab = torch.empty((frames.shape[0], eng.H, eng.W), dtype=torch.uint8, device=dev)
         self.bgr = bgr = eng.bgr_buffer(frames)  # raw ingest: converted into, then read by segment
+        # ... and, with --serve_confidence, the step's own confidence plane
+        self.conf = cf = torch.empty_like(lab) if eng.serve_confidence else None
 
         def segment():
-            return hm.segment(eng.to_bgr(frames, out=bgr), eng.lut_x, eng.lut_y, out=lab, part=part)
+            return hm.segment(eng.to_bgr(frames, out=bgr), eng.lut_x, eng.lut_y, out=lab, part=part,
+                              conf_out=cf)
+
+        def infer():  # no plan (the torch backend): copied into the step's planes
+            labels, conf = eng._infer(frames, bgr)
+            lab.copy_(labels)
+            if cf is not None:
+                cf.copy_(conf)
 
         if eng.slot_parallel:  # SlotStep: this slot's plan copy is built outside capture
             segment()
@@ -73,8 +85,8 @@ class SplitStep:
         if hm is not None:
             self.model, _ = _graph(segment)
         else:
-            self.model, _ = _graph(lambda: lab.copy_(eng._infer_eager(frames, bgr)))
-        self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab))
+            self.model, _ = _graph(infer)
+        self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab, conf=cf))
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
     def replay(self) -> None:
@@ -134,13 +146,16 @@ class PartsStep:
         self.post = post = torch.zeros((B, 1 + 5 * eng.cfg.max_segments), dtype=torch.float32, device=dev)
         self.mask = mask = torch.zeros((B, 4 + eng.mask_cap), dtype=torch.int32,
                                        device=dev) if eng.mask_cap else None
-        self.regions = reg = torch.zeros((B, 4 + 6 * eng.region_cap), dtype=torch.int32,
+        self.regions = reg = torch.zeros((B, 4 + eng.region_words * eng.region_cap), dtype=torch.int32,
                                          device=dev) if eng.region_cap else None
+        self.conf = cf = torch.empty_like(lab) if eng.serve_confidence else None
         parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
-                                                eng.lut_x, eng.lut_y, out=lab[sl], part=i),
+                                                eng.lut_x, eng.lut_y, out=lab[sl], part=i,
+                                                conf_out=cf[sl] if cf is not None else None),
                   lambda sl=sl: eng._device_post(lab[sl], out=post[sl],
                                                  mask_out=mask[sl] if mask is not None else None,
-                                                 region_out=reg[sl] if reg is not None else None))
+                                                 region_out=reg[sl] if reg is not None else None,
+                                                 conf=cf[sl] if cf is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)
         for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
             run()

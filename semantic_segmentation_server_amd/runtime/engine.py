@@ -138,6 +138,14 @@ class Engine:
             RG.check_geometry(self.W, self.H, self.region_min_pixels, self.region_cap)
         self.region_packed: Optional[torch.Tensor] = None
         self.regions: Optional[np.ndarray] = None
+        # --serve_confidence: the model also writes a (B, H, W) uint8 confidence plane
+        # (reference_ops.upsample_confidence) and a region has a 7th word, sum_conf.
+        # conf_plane: the plane of the last run_device / step (a static buffer, like labels)
+        self.serve_confidence = bool(getattr(cfg, "serve_confidence", False))
+        if self.serve_confidence and not cfg.serve_regions:
+            raise ValueError("--serve_confidence requires --serve_regions")
+        self.region_words = 7 if self.serve_confidence else 6
+        self.conf_plane: Optional[torch.Tensor] = None
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -233,17 +241,36 @@ class Engine:
             logits = self.model(x)
         return R.upsample_argmax(logits, self.H, self.W)
 
+    def _infer(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
+        """(label maps, confidence plane) of frames as ingested; without ``serve_confidence``
+        the label maps of ``_infer_eager`` and None."""
+        if not self.serve_confidence:
+            return (self._infer_eager(frames) if bgr is None else self._infer_eager(frames, bgr)), None
+        frames = self.to_bgr(frames, out=bgr)
+        if self.backend == "hip":
+            labels = self._hip_model.segment(frames, self.lut_x, self.lut_y)
+            B, Hc, Wc, _ = frames.shape
+            return labels, self._hip_model.buffers(B, Hc, Wc)["conf"]
+        x = R.preprocess(frames, self.lut_x, self.lut_y,
+                         out_dtype=self.dtype, channels_last=self.is_cuda)
+        with torch.no_grad():
+            logits = self.model(x)
+        return R.upsample_confidence(logits, self.H, self.W)
+
     def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                      mask_out: Optional[torch.Tensor] = None,
-                     region_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._post_and_mask(labels, out, mask_out, region_out)[0]  # the records alone
+                     region_out: Optional[torch.Tensor] = None,
+                     conf: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._post_and_mask(labels, out, mask_out, region_out, conf)[0]  # the records alone
 
     def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                        mask_out: Optional[torch.Tensor] = None,
-                       region_out: Optional[torch.Tensor] = None):
+                       region_out: Optional[torch.Tensor] = None,
+                       conf: Optional[torch.Tensor] = None):
         """(device records of ``labels``, with ``mask_cap`` their run-length masks else None,
         with ``region_cap`` their class regions else None), each right after the other on the
-        same stream: one captured graph, a chain, holds all."""
+        same stream: one captured graph, a chain, holds all. ``conf``: the confidence plane of
+        ``labels`` (``serve_confidence``), summed per region."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -253,9 +280,10 @@ class Engine:
                                                bins=max(1, min(256, self.cfg.num_classes)),
                                                mask_cap=self.mask_cap, region_cap=self.region_cap,
                                                region_classes=self.region_mask,
-                                               region_min_pixels=self.region_min_pixels)
+                                               region_min_pixels=self.region_min_pixels,
+                                               region_conf=self.serve_confidence)
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
-                                 mask_out=mask_out, region_out=region_out)
+                                 mask_out=mask_out, region_out=region_out, conf=conf)
         return (rec, self._hip_post.last_mask if self.mask_cap else None,
                 self._hip_post.last_regions if self.region_cap else None)
 
@@ -272,34 +300,45 @@ class Engine:
             MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
         return out
 
-    def host_regions(self, labels) -> np.ndarray:
+    def host_regions(self, labels, conf=None) -> np.ndarray:
         """uint32 [B, 4 + 6 cap] region words of host label maps by the numpy definition
-        (postprocess/regions.py): the CPU path, and a GPU without device post-processing."""
+        (postprocess/regions.py): the CPU path, and a GPU without device post-processing. With
+        ``serve_confidence``, ``conf`` is their confidence plane and the rows are [B, 4 + 7 cap]."""
         from ..postprocess import regions as RG
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
-        out = np.zeros((lab.shape[0], 4 + 6 * self.region_cap), np.uint32)
+        if self.serve_confidence:
+            if conf is None:
+                raise ValueError("host_regions: serve_confidence needs the conf plane")
+            conf = conf.cpu().numpy() if isinstance(conf, torch.Tensor) else np.asarray(conf)
+        else:
+            conf = None
+        out = np.zeros((lab.shape[0], 4 + self.region_words * self.region_cap), np.uint32)
         for b in range(lab.shape[0]):
             RG.encode(lab[b], self.crop_w, self.crop_h, self.region_mask, self.region_min_pixels,
-                      self.region_cap, out=out[b])
+                      self.region_cap, out=out[b], conf=None if conf is None else conf[b])
         return out
 
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
         """One eager step: (labels, packed records or None, mask run words or None, region
         words or None)."""
-        labels = self._infer_eager(frames, bgr)
+        return self._step_all(frames, bgr)[:4]
+
+    def _step_all(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
+        """``_step_outputs`` and, fifth, the confidence plane (None without ``serve_confidence``)."""
+        labels, conf = self._infer(frames, bgr)
         if self._use_device_post():
-            return (labels, *self._post_and_mask(labels))
+            return (labels, *self._post_and_mask(labels, conf=conf), conf)
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
         host = not self.is_cuda
         mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
-        regions = torch.from_numpy(self.host_regions(labels).view(np.int32)) \
+        regions = torch.from_numpy(self.host_regions(labels, conf).view(np.int32)) \
             if host and self.region_cap else None
         post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
-        return labels, post, mask, regions
+        return labels, post, mask, regions, conf
 
     def _step_device(self, frames: torch.Tensor):
-        labels, post, self.mask_packed, self.region_packed = self._step_outputs(frames)
+        labels, post, self.mask_packed, self.region_packed, self.conf_plane = self._step_all(frames)
         return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
@@ -429,6 +468,7 @@ class Engine:
         step.replay()
         # written by the replay, like the records; and when the frame buffer may be refilled
         self.mask_packed, self.region_packed, self.last_consumed = step.mask, step.regions, step.consumed
+        self.conf_plane = step.conf
         return step.labels, step.post
 
     # ------------------------------------------------------------ post/host
@@ -477,14 +517,14 @@ class Engine:
         if not self.is_cuda:
             frames = torch.from_numpy(np.ascontiguousarray(frames_host))
             with torch.no_grad():
-                labels = self._infer_eager(frames)
+                labels, self.conf_plane = self._infer(frames)
             if self.debug is not None and self.debug.want():
                 self.debug.dump(self._host_bgr(frames_host[0]), labels[0].numpy(), self.crop_w, self.crop_h,
                                 _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))
             if self.mask_cap:
                 self.masks = self.host_masks(labels)
             if self.region_cap:
-                self.regions = self.host_regions(labels)
+                self.regions = self.host_regions(labels, self.conf_plane)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         with torch.cuda.stream(self.stream):
@@ -507,7 +547,7 @@ class Engine:
         if self.mask_cap and post is None:
             self.masks = self.host_masks(labels)
         if self.region_cap and post is None:
-            self.regions = self.host_regions(labels)
+            self.regions = self.host_regions(labels, self.conf_plane)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

@@ -148,7 +148,8 @@ class Producer(threading.Thread):
                         self.hub.push_masks(masks, np.array([ids, streams, ts], np.float64).T)
                     regions = getattr(self.engine, "regions", None)
                     if regions is not None and hasattr(self.hub, "push_regions"):  # --serve_regions
-                        self.hub.push_regions(regions, np.array([ids, streams, ts], np.float64).T)
+                        kw = {"conf": True} if getattr(self.engine, "serve_confidence", False) else {}
+                        self.hub.push_regions(regions, np.array([ids, streams, ts], np.float64).T, **kw)
                 self.metrics.observe("objects_per_frame", len(recs) / max(1, len(ids)))
                 self.metrics.observe("buffer_depth", self.hub.depth)
                 dt = (time.perf_counter() - t0) * 1e3

@@ -141,12 +141,14 @@ class StoredRegions(NamedTuple):
     """A stream's latest class regions: the words are the hub's own copy."""
     frame_id: int
     ts: float
-    words: np.ndarray  # uint32[4 + 6 * stored regions] (postprocess/regions.py)
+    words: np.ndarray  # uint32[4 + 6 * stored regions] (postprocess/regions.py); 7 with conf
+    conf: bool = False  # the records have the seventh word, sum_conf (--serve_confidence)
 
 
 def latest_rows(rows: np.ndarray, meta: np.ndarray, unit: int = 1):
     """Of a collected batch of uint32 rows with a 4-word header whose word 0 counts the
-    payload entries (``unit`` words each; run words: 1, region words: 6), yield per stream
+    payload entries (``unit`` words each; run words: 1, region words: 6, or 7 with
+    confidence), yield per stream
     its LAST frame as (stream, frame id, ts, the row's used words: a view). ``meta``: [F, 3]
     (frame id, stream, capture ts) in the rows' order."""
     rows = np.asarray(rows)
@@ -226,18 +228,21 @@ class ResultHub:
             return self._masks.get(int(stream))
 
     # ---- class regions (--serve_regions): the LATEST region words per stream
-    def put_regions(self, stream: int, frame_id: int, ts: float, words: np.ndarray) -> None:
+    def put_regions(self, stream: int, frame_id: int, ts: float, words: np.ndarray,
+                    conf: bool = False) -> None:
         """Store a COPY of ``words`` (header + stored records, postprocess/regions.py) as the
-        stream's latest regions."""
-        r = StoredRegions(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True))
+        stream's latest regions. ``conf``: the records have 7 words (``sum_conf``)."""
+        r = StoredRegions(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True),
+                          bool(conf))
         with self._lock:
             self._regions[int(stream)] = r
 
-    def push_regions(self, rows: np.ndarray, meta: np.ndarray) -> None:
+    def push_regions(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False) -> None:
         """As ``push_masks`` for [F, 4 + 6 K] region words: of several frames of one stream
-        only the last is copied, and only its ``4 + 6 * min(n_regions, K)`` used words."""
-        for st, fid, ts, words in latest_rows(rows, meta, 6):
-            self.put_regions(st, fid, ts, words)
+        only the last is copied, and only its ``4 + 6 * min(n_regions, K)`` used words. With
+        ``conf`` the rows are [F, 4 + 7 K] (``sum_conf``), and stored as such."""
+        for st, fid, ts, words in latest_rows(rows, meta, 7 if conf else 6):
+            self.put_regions(st, fid, ts, words, conf)
 
     def regions(self, stream: int) -> Optional["StoredRegions"]:
         """The stream's latest regions (frame_id, ts, words), or None before the first ones."""
