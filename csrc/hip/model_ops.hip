@@ -1179,7 +1179,10 @@ void upsample_argmax(const bf16* logits, uint8_t* labels, int B, int h, int w, i
   // interval path: at most 32 output pixels share a left source column; the row-block
   // variant needs a whole row of intervals in one workgroup and R * W bytes of LDS
   const float sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-  const bool interval = K <= 32 && ldk % 8 == 0 && ldk >= ((K + 7) / 8) * 8 && w >= 2 && W > 1 &&
+  // Interval::load reads KP channels of every source pixel in 16-byte vectors whatever K is:
+  // the rows must hold them (K <= 16 in rows of 8 or 16 would read past the last pixel)
+  const int kp = K <= 24 ? 24 : 32;
+  const bool interval = K <= 32 && ldk % 8 == 0 && ldk >= kp && w >= 2 && W > 1 &&
                         sw > 0.f && 1.f / sw <= 30.f && (long long)B * H * w < (1LL << 31);
   if (interval && (variant == 3 || variant == 4) && (w > 256 || (256 / w) * W > 65536))
     variant -= 2;

@@ -20,11 +20,11 @@ import torch
 import torch.nn.functional as F
 
 from semantic_segmentation_server_amd.postprocess import regions as RG
+from upsample_ref import GUARD, guarded as _guarded, ref64 as _ref64
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-GUARD = 0xEE
 SENT = 0x5A5A5A5A
 WS_SENT = 0xA5
 WS_TAIL = 256
@@ -57,21 +57,6 @@ def _logits(B, h, w, K, field):
             .permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
     logits[..., K:] = 100.0
     return logits, ldk
-
-
-def _ref64(logits, K, H, W):
-    """(255 * p64, float64 argmax, top-two margin) of NHWC bf16 logits."""
-    u = F.interpolate(logits[..., :K].double().permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
-                      align_corners=True)
-    p = torch.softmax(u, 1).amax(1)
-    top2 = u.topk(2, dim=1).values
-    return 255.0 * p, u.argmax(1), top2[:, 0] - top2[:, 1]
-
-
-def _guarded(B, H, W):
-    """A contiguous (B, H, W) uint8 plane with one guard row of 0xEE before and after."""
-    raw = torch.full((B * H + 2, W), GUARD, dtype=torch.uint8, device=DEV)
-    return raw, raw[1:-1].view(B, H, W)
 
 
 def _assert_conf(conf, labels, c64, a64, margin, input_condition=True):
