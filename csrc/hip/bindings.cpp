@@ -477,6 +477,28 @@ PYBIND11_MODULE(_hip, m) {
   m.attr("REGION_TILE") = class_regions_tile();
   m.attr("REGION_CANDIDATES") = class_regions_candidates();
 
+  m.def("region_tracks_workspace_bytes", &region_tracks_workspace_bytes, py::arg("B"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("K"));
+  m.def("region_tracks_state_bytes", &region_tracks_state_bytes, py::arg("streams"),
+        py::arg("crop_h"), py::arg("crop_w"));
+  m.def("region_tracks",
+        [](uintptr_t ws, uintptr_t rows, uintptr_t out, uintptr_t tws, uintptr_t state, uintptr_t pred,
+           uintptr_t stream_of, uintptr_t last, int B, int streams, int crop_h, int crop_w, int K,
+           int record_words, int q, uintptr_t stream, int kernels) {
+          RegionTracksParams p;
+          p.kernels = kernels;
+          p.ws = P<const uint32_t>(ws); p.rows = P<const uint32_t>(rows); p.out = P<uint32_t>(out);
+          p.tws = P<uint32_t>(tws); p.state = P<uint32_t>(state);
+          p.pred = P<const int>(pred); p.stream = P<const int>(stream_of); p.last = P<const int>(last);
+          p.B = B; p.streams = streams; p.crop_h = crop_h; p.crop_w = crop_w; p.K = K;
+          p.record_words = record_words; p.q = q;
+          region_tracks(p, S(stream));
+        },
+        py::arg("ws"), py::arg("rows"), py::arg("out"), py::arg("tws"), py::arg("state"),
+        py::arg("pred"), py::arg("stream_of"), py::arg("last"), py::arg("B"), py::arg("streams"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("K"), py::arg("record_words"), py::arg("q"),
+        py::arg("stream"), py::arg("kernels") = 31);
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

@@ -500,6 +500,291 @@ __global__ __launch_bounds__(kMaxK) void k_cr_emit(CrArgs a) {
   }
 }
 
+// ---- region tracks (postprocess/tracks.py is the definition) --------------------------------
+// Five launches that follow k_cr_emit in the same chain; they read what the class-region
+// kernels leave (the final parent[], cnt[root] = kSlotBit | rank of the stored regions, the
+// records) and change none of it. `rows` are the records of this run ([B, 4 + RW K]), `out`
+// the rows with tracks ([B, 4 + (RW + 2) K]): the record's words, then track_id and age.
+//   k_tr_slots    S[b][i], a uint16 plane per frame: the rank of pixel i's stored region,
+//                 kNoSlot without one. Its blocks also zero the rows of the frame's overlap
+//                 table that are used (n_t x K words).
+//   k_tr_overlap  per frame, a pass over S[b] and the plane of the stream's previous frame:
+//                 S[pred[b]] of this batch, or the stream's carried plane. The pixels are
+//                 taken in flat order (an overlap count knows no geometry): one LDS atomic per
+//                 run of an equal (a, b') key inside a wave (one ballot), into a hash table of
+//                 the block's chunk, then one global integer atomic per key and block. A key
+//                 that finds no entry within kProbes goes to the global table directly.
+//   k_tr_carry    copies the plane of each stream's last frame of the batch to its state.
+//   k_tr_match    one workgroup per frame: best and winner from the table, link[b][a] = the
+//                 predecessor of a matched region; copies the record words to the wide rows.
+//   k_tr_assign   one workgroup per stream, its frames in batch order: ids and ages from the
+//                 previous frame's (LDS; first the carried state's), new ids by a ballot scan,
+//                 the two words of every stored record, then the carried state.
+// Per stream the state is [n, issued, pad, pad, track_id[kMaxK], age[kMaxK], label[kMaxK],
+// pixels[kMaxK]] words and a plane of plane_words(N) words; all zero: no predecessor, nothing
+// issued. A stream without a row in the batch keeps its state.
+constexpr uint32_t kNoSlot = 0xFFFFu;
+constexpr int kStateHead = 4 + 4 * kMaxK;
+constexpr int kOvPix = 16;                      // pixels per thread of an overlap block
+constexpr int kOvChunk = kThreads * kOvPix;
+constexpr int kHash = 1024;
+constexpr int kProbes = 16;
+
+__host__ __device__ __forceinline__ size_t plane_words(size_t N) { return (N + 3) / 4 * 2; }  // 8-byte multiple
+__host__ __device__ __forceinline__ size_t state_words(size_t N) { return kStateHead + plane_words(N); }
+
+struct TrArgs {
+  const uint32_t* ws;    // of class_regions, after its run
+  const uint32_t* rows;  // [B, 4 + RW K]
+  uint32_t* out;         // [B, 4 + (RW + 2) K]
+  uint32_t* tws;         // planes [B][plane_words], then tables [B][K][K], then links [B][K]
+  uint32_t* state;       // [S][state_words]
+  const int* pred;       // [B]
+  const int* stream;     // [B]
+  const int* last;       // [S]
+  int B, S, K, N, RW;
+  uint32_t q;
+};
+
+__device__ __forceinline__ uint16_t* tr_plane(const TrArgs& t, int b) {
+  return reinterpret_cast<uint16_t*>(t.tws + (size_t)b * plane_words((size_t)t.N));
+}
+__device__ __forceinline__ uint32_t* tr_table(const TrArgs& t, int b) {
+  return t.tws + (size_t)t.B * plane_words((size_t)t.N) + (size_t)b * t.K * t.K;
+}
+__device__ __forceinline__ uint32_t* tr_state(const TrArgs& t, int s) {
+  return t.state + (size_t)s * state_words((size_t)t.N);
+}
+__device__ __forceinline__ uint32_t tr_stored(const TrArgs& t, int b) {  // min(n_regions, K)
+  const uint32_t n = t.rows[(size_t)b * (4 + t.RW * t.K)];
+  return n < (uint32_t)t.K ? n : (uint32_t)t.K;
+}
+
+__global__ __launch_bounds__(kThreads) void k_tr_slots(TrArgs t) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  uint32_t* tab = tr_table(t, b);
+  const uint32_t used = tr_stored(t, b) * (uint32_t)t.K;
+  for (uint32_t j = (uint32_t)i; j < used; j += gridDim.x * kThreads) tab[j] = 0;
+  if (i >= t.N) return;
+  const uint32_t* parent = t.ws + (size_t)b * frame_words((size_t)t.N);
+  const uint32_t* cnt = parent + t.N;
+  uint32_t slot = kNoSlot;
+  if (parent[i] != kNone) {
+    const uint32_t c = cnt[find_plain(parent, (uint32_t)i)];
+    if (c & kSlotBit) slot = c & ~kSlotBit;
+  }
+  tr_plane(t, b)[i] = (uint16_t)slot;
+}
+
+__global__ __launch_bounds__(kThreads) void k_tr_overlap(TrArgs t) {
+  __shared__ uint32_t hkey[kHash];
+  __shared__ uint32_t hcnt[kHash];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int p = t.pred[b];
+  const uint32_t n_cur = tr_stored(t, b);
+  const uint16_t* prev;
+  uint32_t n_prev;
+  if (p >= 0) {
+    prev = tr_plane(t, p);
+    n_prev = tr_stored(t, p);
+  } else {
+    const uint32_t* st = tr_state(t, t.stream[b]);
+    prev = reinterpret_cast<const uint16_t*>(st + kStateHead);
+    n_prev = st[0] < (uint32_t)t.K ? st[0] : (uint32_t)t.K;
+  }
+  if (n_cur == 0 || n_prev == 0) return;  // by the whole block
+  for (int j = tid; j < kHash; j += kThreads) {
+    hkey[j] = kNone;
+    hcnt[j] = 0;
+  }
+  __syncthreads();
+  const uint16_t* cur = tr_plane(t, b);
+  uint32_t* tab = tr_table(t, b);
+  const int lane = tid & 63;
+  const int base = blockIdx.x * kOvChunk + (tid >> 6) * (64 * kOvPix);  // a wave: 64 x kOvPix pixels in a row
+#pragma unroll 4
+  for (int k = 0; k < kOvPix; ++k) {
+    const int i = base + k * 64 + lane;
+    uint32_t key = kNone;
+    if (i < t.N) {
+      const uint32_t a = cur[i], bp = prev[i];
+      if (a < n_cur && bp < n_prev) key = a * (uint32_t)t.K + bp;
+    }
+    const uint32_t left = (uint32_t)__shfl_up((int)key, 1, 64);  // by every lane, before any branch
+    const bool head = lane == 0 || left != key;
+    const unsigned long long heads = __ballot(head);
+    if (!head || key == kNone) continue;
+    const unsigned long long after = lane == 63 ? 0ull : heads >> (lane + 1);
+    const uint32_t n = after ? (uint32_t)__ffsll((long long)after) : (uint32_t)(64 - lane);
+    uint32_t h = (key * 2654435761u) >> 22;  // kHash = 2^10
+    bool done = false;
+    for (int probe = 0; probe < kProbes && !done; ++probe, h = (h + 1) & (kHash - 1)) {
+      const uint32_t old = atomicCAS(&hkey[h], kNone, key);
+      if (old == kNone || old == key) {
+        atomicAdd(&hcnt[h], n);
+        done = true;
+      }
+    }
+    if (!done) atomicAdd(tab + key, n);
+  }
+  __syncthreads();
+  for (int j = tid; j < kHash; j += kThreads)
+    if (hkey[j] != kNone) atomicAdd(tab + hkey[j], hcnt[j]);
+}
+
+__global__ __launch_bounds__(kThreads) void k_tr_carry(TrArgs t) {
+  const int s = blockIdx.y;
+  const int r = t.last[s];
+  if (r < 0) return;
+  const size_t w = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (w >= plane_words((size_t)t.N)) return;
+  (tr_state(t, s) + kStateHead)[w] = (t.tws + (size_t)r * plane_words((size_t)t.N))[w];
+}
+
+// best, winner and matched of every frame, in parallel over the frames: link[b][a] = best[a] if
+// a is matched, else kNone. A wave takes a region a at a time, its lanes the predecessors b'
+// (coalesced table reads); (overlap, ~index) packed in 64 bits makes "largest overlap, then the
+// smaller index" one maximum, over the lanes by shuffles and per b' by one LDS atomic. The frame's
+// header and record words are copied to the rows with tracks here too.
+__global__ __launch_bounds__(kMaxK) void k_tr_match(TrArgs t) {
+  __shared__ uint32_t p_lab[kMaxK], p_pix[kMaxK], best[kMaxK];
+  __shared__ unsigned long long wkey[kMaxK];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int RW = t.RW, OW = t.RW + 2;
+  const uint32_t* row = t.rows + (size_t)b * (4 + RW * t.K);
+  uint32_t* o = t.out + (size_t)b * (4 + OW * t.K);
+  const uint32_t n_cur = tr_stored(t, b);
+  const int p = t.pred[b];
+  uint32_t n_prev;
+  if (p >= 0) {
+    const uint32_t* prow = t.rows + (size_t)p * (4 + RW * t.K);
+    n_prev = tr_stored(t, p);
+    if ((uint32_t)tid < n_prev) {
+      p_lab[tid] = prow[4 + RW * tid] >> 24;
+      p_pix[tid] = prow[4 + RW * tid + 1];
+    }
+  } else {
+    const uint32_t* st = tr_state(t, t.stream[b]);
+    n_prev = st[0] < (uint32_t)t.K ? st[0] : (uint32_t)t.K;
+    if ((uint32_t)tid < n_prev) {
+      p_lab[tid] = st[4 + 2 * kMaxK + tid];
+      p_pix[tid] = st[4 + 3 * kMaxK + tid];
+    }
+  }
+  wkey[tid] = 0ull;
+  best[tid] = kNone;
+  if (tid < 4) o[tid] = row[tid];
+  for (uint32_t w = (uint32_t)tid; w < n_cur * (uint32_t)RW; w += kMaxK) {
+    const uint32_t a = w / (uint32_t)RW;
+    o[4 + OW * a + (w - a * RW)] = row[4 + w];
+  }
+  __syncthreads();
+  const uint32_t* tab = tr_table(t, b);
+  for (uint32_t a = (uint32_t)tid >> 6; a < n_cur; a += kMaxK / 64) {  // by whole waves
+    const uint32_t lab = row[4 + RW * a] >> 24, pix = row[4 + RW * a + 1];
+    unsigned long long k = 0ull;
+    for (uint32_t j = (uint32_t)lane; j < n_prev; j += 64) {
+      if (p_lab[j] != lab) continue;
+      const uint32_t ov = tab[(size_t)a * t.K + j];
+      const uint32_t lo = pix < p_pix[j] ? pix : p_pix[j];
+      if (ov > 0 && 1024ull * ov >= (unsigned long long)t.q * lo) {
+        const unsigned long long c = ((unsigned long long)ov << 32) | (uint32_t)~j;
+        k = c > k ? c : k;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long c = (unsigned long long)__shfl_xor((long long)k, off, 64);
+      k = c > k ? c : k;
+    }
+    if (lane == 0 && k != 0ull) {
+      const uint32_t bb = ~(uint32_t)k;
+      best[a] = bb;
+      atomicMax(&wkey[bb], (k & 0xFFFFFFFF00000000ull) | (uint32_t)~a);
+    }
+  }
+  __syncthreads();
+  if ((uint32_t)tid < n_cur) {
+    const uint32_t bb = best[tid];
+    t.tws[(size_t)t.B * plane_words((size_t)t.N) + (size_t)t.B * t.K * t.K + (size_t)b * t.K + tid] =
+        (bb != kNone && ~(uint32_t)wkey[bb] == (uint32_t)tid) ? bb : kNone;
+  }
+}
+
+// One workgroup per stream: the short chain over its frames in batch order. Thread a takes the
+// id and age of its predecessor (LDS; for the first frame the carried state's) or a new id, by
+// a ballot scan over the unmatched regions, and writes the two words; then the carried state.
+__global__ __launch_bounds__(kMaxK) void k_tr_assign(TrArgs t) {
+  __shared__ uint32_t p_id[2][kMaxK], p_age[2][kMaxK];
+  __shared__ uint32_t wave_new[2][kMaxK / 64];
+  const int s = blockIdx.x, a = threadIdx.x;
+  const int r1 = t.last[s];
+  if (r1 < 0) return;  // no row of this stream in the batch: its state stays
+  int r0 = r1;
+  while (t.pred[r0] >= 0) r0 = t.pred[r0];
+  uint32_t* st = tr_state(t, s);
+  uint32_t issued = st[1];
+  p_id[0][a] = st[4 + a];
+  p_age[0][a] = st[4 + kMaxK + a];
+  const uint32_t* links = t.tws + (size_t)t.B * plane_words((size_t)t.N) + (size_t)t.B * t.K * t.K;
+  const int RW = t.RW, OW = t.RW + 2;
+  uint32_t n_cur = tr_stored(t, r0);
+  uint32_t link = (uint32_t)a < n_cur ? links[(size_t)r0 * t.K + a] : kNone;
+  __syncthreads();
+  int cur = 0;
+  for (int r = r0; r <= r1; ++r, cur ^= 1) {  // consecutive rows (the host builds pred so)
+    const bool on = (uint32_t)a < n_cur, matched = on && link != kNone, fresh = on && !matched;
+    uint32_t n_next = 0, link_next = kNone;  // the next frame's, loaded under this one's work
+    if (r < r1) {
+      n_next = tr_stored(t, r + 1);
+      if ((uint32_t)a < n_next) link_next = links[(size_t)(r + 1) * t.K + a];
+    }
+    const unsigned long long m = __ballot(fresh);
+    if ((a & 63) == 0) wave_new[cur][a >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();  // one barrier a frame (the arrays alternate): also orders the previous
+    uint32_t id = 0, age = 0;  // frame's ids and ages before these reads
+    if (matched) {
+      id = p_id[cur][link];
+      age = p_age[cur][link] + 1;
+    }
+    uint32_t before = (uint32_t)__popcll(m & ((1ull << (a & 63)) - 1ull)), total = 0;
+#pragma unroll
+    for (int w = 0; w < kMaxK / 64; ++w) {
+      if (w < (a >> 6)) before += wave_new[cur][w];
+      total += wave_new[cur][w];
+    }
+    if (fresh) {
+      id = issued + 1 + before;
+      age = 1;
+    }
+    issued += total;
+    if (on) {
+      uint32_t* o = t.out + (size_t)r * (4 + OW * t.K) + 4 + OW * a + RW;
+      o[0] = id;
+      o[1] = age;
+    }
+    p_id[cur ^ 1][a] = id;
+    p_age[cur ^ 1][a] = age;
+    if (r < r1) {
+      n_cur = n_next;
+      link = link_next;
+    }
+  }
+  __syncthreads();
+  st[4 + a] = p_id[cur][a];
+  st[4 + kMaxK + a] = p_age[cur][a];
+  const uint32_t* row = t.rows + (size_t)r1 * (4 + RW * t.K);
+  if ((uint32_t)a < n_cur) {
+    st[4 + 2 * kMaxK + a] = row[4 + RW * a] >> 24;
+    st[4 + 3 * kMaxK + a] = row[4 + RW * a + 1];
+  }
+  if (a == 0) {
+    st[0] = n_cur;
+    st[1] = issued;
+  }
+}
+
 }  // namespace
 
 int class_regions_tile() { return kTile; }
@@ -540,6 +825,36 @@ void class_regions(const ClassRegionsParams& p, hipStream_t s) {
     hipLaunchKernelGGL(k_cr_emit<false>, dim3(p.B), dim3(kMaxK), 0, s, a);
   }
   check_launch("class_regions");
+}
+
+size_t region_tracks_workspace_bytes(int B, int crop_h, int crop_w, int K) {
+  const size_t N = (size_t)crop_h * (size_t)crop_w;
+  return ((size_t)B * plane_words(N) + (size_t)B * K * K + (size_t)B * K) * sizeof(uint32_t);
+}
+
+size_t region_tracks_state_bytes(int streams, int crop_h, int crop_w) {
+  return (size_t)streams * state_words((size_t)crop_h * (size_t)crop_w) * sizeof(uint32_t);
+}
+
+void region_tracks(const RegionTracksParams& p, hipStream_t s) {
+  const long long N = (long long)p.crop_h * p.crop_w;
+  if (p.B <= 0 || p.B > 65535 || p.streams <= 0 || p.streams > 65535 || p.crop_h <= 0 ||
+      p.crop_w <= 0 || N >= (1LL << 24) || p.K < 1 || p.K > kMaxK ||
+      (p.record_words != 6 && p.record_words != 7) || p.q < 1 || p.q > 1024 || !p.ws || !p.rows ||
+      !p.out || !p.tws || !p.state || !p.pred || !p.stream || !p.last)
+    check(hipErrorInvalidValue, "region_tracks: bad arguments");
+  TrArgs t;
+  t.ws = p.ws; t.rows = p.rows; t.out = p.out; t.tws = p.tws; t.state = p.state;
+  t.pred = p.pred; t.stream = p.stream; t.last = p.last;
+  t.B = p.B; t.S = p.streams; t.K = p.K; t.N = (int)N; t.RW = p.record_words; t.q = (uint32_t)p.q;
+  if (p.kernels & 1) hipLaunchKernelGGL(k_tr_slots, dim3(cdiv(N, kThreads), p.B), dim3(kThreads), 0, s, t);
+  if (p.kernels & 2) hipLaunchKernelGGL(k_tr_overlap, dim3(cdiv(N, kOvChunk), p.B), dim3(kThreads), 0, s, t);
+  if (p.kernels & 4)
+    hipLaunchKernelGGL(k_tr_carry, dim3(cdiv((long long)plane_words((size_t)N), kThreads), p.streams),
+                       dim3(kThreads), 0, s, t);
+  if (p.kernels & 8) hipLaunchKernelGGL(k_tr_match, dim3(p.B), dim3(kMaxK), 0, s, t);
+  if (p.kernels & 16) hipLaunchKernelGGL(k_tr_assign, dim3(p.streams), dim3(kMaxK), 0, s, t);
+  check_launch("region_tracks");
 }
 
 }  // namespace ssa

@@ -378,4 +378,29 @@ int class_regions_tile();        // tile edge of the tile-local pass
 int class_regions_candidates();  // most regions that may pass in one frame
 void class_regions(const ClassRegionsParams& p, hipStream_t s);
 
+// ---- region tracks (class_regions.hip; the definition is postprocess/tracks.py) -------------
+// After class_regions on the same stream: the stored regions of every frame are matched to
+// those of the stream's previous frame by exact pixel overlap, and `out` gets the rows with
+// two more words a record, track_id and age: [B, 4 + (record_words + 2) K]. `rows`, `ws`: the
+// output and the workspace of that class_regions run (K, crop and B the same). The rows of a
+// stream are consecutive; pred[b] is the row of the stream's previous frame in this batch or
+// -1 (the carried state), stream[b] its stream, last[s] the last row of stream s or -1.
+// `state` is carried from run to run (region_tracks_state_bytes; all zero: no predecessor,
+// nothing issued); `tws` is scratch. q = round(1024 * min overlap ratio), 1 .. 1024.
+struct RegionTracksParams {
+  const uint32_t* ws = nullptr;
+  const uint32_t* rows = nullptr;
+  uint32_t* out = nullptr;
+  uint32_t* tws = nullptr;    // region_tracks_workspace_bytes(B, crop_h, crop_w, K)
+  uint32_t* state = nullptr;  // region_tracks_state_bytes(streams, crop_h, crop_w)
+  const int* pred = nullptr;
+  const int* stream = nullptr;
+  const int* last = nullptr;
+  int B = 0, streams = 0, crop_h = 0, crop_w = 0, K = 0, record_words = 6, q = 256;
+  int kernels = 31;  // which of slots (1), overlap (2), carry (4), match (8), assign (16) to launch: all but for timing
+};
+size_t region_tracks_workspace_bytes(int B, int crop_h, int crop_w, int K);
+size_t region_tracks_state_bytes(int streams, int crop_h, int crop_w);
+void region_tracks(const RegionTracksParams& p, hipStream_t s);
+
 }  // namespace ssa

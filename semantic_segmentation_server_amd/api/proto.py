@@ -166,6 +166,10 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "y_max", 10, F.TYPE_FLOAT)
     # mean winning-class softmax probability of the region's pixels (--serve_confidence; else 0)
     _field(m, "confidence", 11, F.TYPE_FLOAT)
+    # identity of the region across the stream's frames and the frames it has lived
+    # (--track_regions, postprocess/tracks.py; else 0)
+    _field(m, "track_id", 12, F.TYPE_UINT32)
+    _field(m, "age", 13, F.TYPE_UINT32)
 
     # the regions of the stream's latest frame, by (pixels descending, first pixel ascending)
     m = fd.message_type.add(); m.name = "ClassRegions"
@@ -180,6 +184,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "total_regions", 9, F.TYPE_UINT32)  # regions that passed; more than stored: truncated
     _field(m, "truncated", 10, F.TYPE_BOOL)
     _field(m, "has_confidence", 11, F.TYPE_BOOL)  # the regions carry a confidence
+    _field(m, "has_tracks", 12, F.TYPE_BOOL)      # the regions carry track_id and age
 
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"

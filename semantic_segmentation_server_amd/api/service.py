@@ -145,7 +145,8 @@ class SemanticSegmentationV2Servicer:
             context.set_details(f"no frame of stream {stream} collected yet")
             return P.ClassRegions()
         has_conf = bool(getattr(r, "conf", False))
-        tab = RG.decode(r.words, conf=has_conf)
+        has_tracks = bool(getattr(r, "tracks", False))
+        tab = RG.decode(r.words, conf=has_conf, tracks=has_tracks)
         total = int(r.words[0])
         if request.max_regions > 0:
             tab = tab[:int(request.max_regions)]
@@ -159,12 +160,13 @@ class SemanticSegmentationV2Servicer:
                 cy=(int(t["sum_y"]) / px + 0.5) / mh, x_min=int(t["x_min"]) / mw,
                 y_min=int(t["y_min"]) / mh, x_max=(int(t["x_max"]) + 1) / mw,
                 y_max=(int(t["y_max"]) + 1) / mh,
-                confidence=int(t["sum_conf"]) / (255 * px) if has_conf else 0.0))
+                confidence=int(t["sum_conf"]) / (255 * px) if has_conf else 0.0,
+                track_id=int(t["track_id"]), age=int(t["age"])))
         return P.ClassRegions(
             stream_id=stream, frame_id=r.frame_id, timestamp=r.ts, width=int(r.words[2]),
             height=int(r.words[3]), model_width=int(self.model_size[0]),
             model_height=int(self.model_size[1]), regions=out, total_regions=total,
-            truncated=len(out) < total, has_confidence=has_conf)
+            truncated=len(out) < total, has_confidence=has_conf, has_tracks=has_tracks)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

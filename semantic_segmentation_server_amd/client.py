@@ -108,7 +108,8 @@ def print_regions(m) -> None:
         print("  {:>3} {:<20} {:>8} px  area {:.4f}  centre ({:.3f}, {:.3f})  box ({:.3f}, {:.3f}) - "
               "({:.3f}, {:.3f})".format(r.class_id, r.label, r.pixels, r.area, r.cx, r.cy, r.x_min,
                                        r.y_min, r.x_max, r.y_max) +
-              ("  conf {:.3f}".format(r.confidence) if m.has_confidence else ""))
+              ("  conf {:.3f}".format(r.confidence) if m.has_confidence else "") +
+              ("  track {:>5}  age {:>5}".format(r.track_id, r.age) if m.has_tracks else ""))
 
 
 def main(argv=None) -> int:

@@ -68,6 +68,8 @@ class Config:
     region_min_area_ratio: float = 0.002   # smallest region served, as a share of input_size^2
     region_classes: Optional[str] = None   # comma list of class ids / label names; None: all but 0
     serve_confidence: bool = False         # per-pixel confidence on the device, served per class region
+    track_regions: bool = False            # match the regions of consecutive frames: track_id, age per region
+    track_min_overlap: float = 0.25        # overlap / smaller region that continues a track, in (0, 1]
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -92,6 +94,11 @@ class Config:
         if self.serve_confidence and not self.serve_regions:
             raise ValueError("--serve_confidence requires --serve_regions: the confidence is served "
                              "per class region (v2 GetClassRegions)")
+        if self.track_regions and not self.serve_regions:
+            raise ValueError("--track_regions requires --serve_regions: a track is the identity of a "
+                             "class region across frames (v2 GetClassRegions)")
+        if self.track_regions and not 0.0 < float(self.track_min_overlap) <= 1.0:
+            raise ValueError(f"--track_min_overlap {self.track_min_overlap} outside (0, 1]")
         if self.pixel_format != "bgr":
             if self.camera_width % 2:
                 raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
@@ -184,6 +191,13 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="compute the winning class's softmax probability of every pixel on the "
                         "device and serve its mean per class region (v2 GetClassRegions "
                         "confidence); requires --serve_regions")
+    p.add_argument("--track_regions", action="store_true",
+                   help="match the class regions of each stream's consecutive frames by pixel "
+                        "overlap on the device and serve a track id and an age per region (v2 "
+                        "GetClassRegions track_id, age); requires --serve_regions")
+    p.add_argument("--track_min_overlap", type=float, default=d.track_min_overlap,
+                   help="smallest overlap, as a share of the smaller of two regions, that "
+                        "continues a track (0 < ratio <= 1)")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

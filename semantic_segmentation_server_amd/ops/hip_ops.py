@@ -1325,6 +1325,80 @@ def class_regions(labels, out, ws, *, B, H, W, crop_h, crop_w, classes, min_pixe
     return out
 
 
+def region_tracks_workspace_bytes(B, crop_h, crop_w, K) -> int:
+    return int(_hip_mod().region_tracks_workspace_bytes(B, crop_h, crop_w, K))
+
+
+def region_tracks_state_bytes(streams, crop_h, crop_w) -> int:
+    return int(_hip_mod().region_tracks_state_bytes(streams, crop_h, crop_w))
+
+
+def region_track_tables(counts, device) -> torch.Tensor:
+    """The batch layout of ``region_tracks`` on the device: int32 [pred[B] | stream[B] | last[S]]
+    from the rows each stream owns (postprocess/tracks.py ``batch_tables``)."""
+    import numpy as np
+    from ..postprocess import tracks as TK
+    return torch.from_numpy(np.concatenate(TK.batch_tables(counts))).to(device)
+
+
+REGION_TRACK_KERNELS = {"slots": 1, "overlap": 2, "carry": 4, "match": 8, "assign": 16}
+
+
+def region_tracks(rows, out, ws, tws, state, tables, *, counts, crop_h, crop_w, K, q, conf=False,
+                  kernels: int = 31):
+    """Track ids of the class regions that ``class_regions`` just wrote on the current stream
+    (the ``k_tr_*`` kernels of csrc/hip/class_regions.hip; postprocess/tracks.py is the
+    definition). ``rows`` / ``ws``: that run's output [B, 4 + 6 K] (7 with ``conf``) and
+    workspace; ``out``: int32/uint32 [B, 4 + 8 K] (9), the records followed by track_id and age.
+    ``counts``: the rows each stream owns, consecutive, in stream order (B is their sum);
+    ``tables``: ``region_track_tables(counts)``; ``tws``: scratch of at least
+    ``region_tracks_workspace_bytes``; ``state``: the streams' carried state, exactly
+    ``region_tracks_state_bytes(len(counts), crop_h, crop_w)`` bytes (zero: a reset).
+    ``q``: ``tracks.quantize(min overlap)``. ``kernels``: a mask over REGION_TRACK_KERNELS of the
+    launches to issue -- all of them, except where one is timed alone (scripts/tracks_bench.py)."""
+    from ..postprocess import regions as RG
+    counts = [int(c) for c in counts]
+    if not counts or min(counts) < 0:
+        raise ValueError(f"region_tracks: bad layout {counts}")
+    B, S = sum(counts), len(counts)
+    if B < 1 or B > 65535 or S > 65535:
+        raise ValueError(f"region_tracks: bad batch {B} of {S} streams")
+    if crop_h < 1 or crop_w < 1 or crop_h * crop_w >= RG.MAX_PIXELS:
+        raise ValueError(f"region_tracks: bad crop {crop_h} x {crop_w}")
+    if not 1 <= K <= REGION_MAX_K:
+        raise ValueError(f"region_tracks: K {K} outside 1 .. {REGION_MAX_K}")
+    if not 1 <= int(q) <= 1024:
+        raise ValueError(f"region_tracks: q {q} outside 1 .. 1024")
+    if not 1 <= int(kernels) <= 31:
+        raise ValueError(f"region_tracks: kernels {kernels} outside 1 .. 31")
+    rw = 7 if conf else 6
+    for t, name, width in ((rows, "rows", rw), (out, "out", rw + 2)):
+        if t.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"{name}: expected uint32 or int32, got {t.dtype}")
+        _chk(t, t.dtype, name)
+        if tuple(t.shape) != (B, 4 + width * K):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {4 + width * K})")
+    if rows.data_ptr() == out.data_ptr():
+        raise ValueError("region_tracks: rows and out are the same buffer")
+    _chk(ws, torch.uint8, "ws", class_regions_workspace_bytes(B, crop_h, crop_w, bool(conf)))
+    _chk(tws, torch.uint8, "tws", region_tracks_workspace_bytes(B, crop_h, crop_w, K))
+    _chk(state, torch.uint8, "state")
+    if state.numel() != region_tracks_state_bytes(S, crop_h, crop_w):
+        raise ValueError(f"state: {state.numel()} bytes != {region_tracks_state_bytes(S, crop_h, crop_w)}")
+    _chk(tables, torch.int32, "tables")
+    if tables.numel() != 2 * B + S:
+        raise ValueError(f"tables: {tables.numel()} words != 2 * {B} + {S}")
+    for t in (out, ws, tws, state, tables):
+        if t.device != rows.device:
+            raise ValueError("region_tracks: the buffers are on different devices")
+    p = _ptr(tables)
+    _hip_mod().region_tracks(_ptr(ws), _ptr(rows), _ptr(out), _ptr(tws), _ptr(state), p, p + 4 * B,
+                             p + 8 * B, B, S, int(crop_h), int(crop_w), int(K), rw, int(q), _stream(),
+                             int(kernels))
+    _dbg('region_tracks')
+    return out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

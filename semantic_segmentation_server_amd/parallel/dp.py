@@ -186,7 +186,17 @@ class DataParallelPipeline:
         self.region_cap = int(getattr(engine, "region_cap", 0) or 0)
         # --serve_confidence: 7 words a region (sum_conf); the hub is told so with every push
         self.region_words = int(getattr(engine, "region_words", 6) or 6)
-        self._region_kw = {"conf": True} if self.region_words == 7 else {}
+        # --track_regions: two more words a region (track_id, age), also told with every push.
+        # The engine's tracking kernels are built for one batch layout (consecutive rows per
+        # stream): every step's streams are checked against it
+        self.track = bool(getattr(engine, "track_regions", False))
+        self._region_kw = {"conf": True} if getattr(engine, "serve_confidence", self.region_words == 7) else {}
+        if self.track:
+            self._region_kw["tracks"] = True
+            if ctx.initialized and ctx.world > 1:
+                raise ValueError("track_regions is not supported in a multi-rank group (world size "
+                                 f"{ctx.world}): class regions and their tracks are not gathered "
+                                 "across ranks; run one GPU, or the supervised server")
         if self.region_cap and ctx.initialized and ctx.world > 1:
             raise ValueError("serve_regions is not supported in a multi-rank group (world size "
                              f"{ctx.world}): class regions are not gathered across ranks; run one "
@@ -334,6 +344,8 @@ class DataParallelPipeline:
         if self.cuda and hasattr(engine, "bind_inputs"):
             if engine.slot_parallel:
                 self._prime(int(os.environ.get("SSA_PIPE_PRIME", str(8 * self.nslots))))
+        if self.track:  # a pipeline starts: its first frames are the streams' first
+            engine.reset_tracks()
 
     def rccl_nranks(self) -> Optional[int]:
         """Ranks in the pipeline's RCCL communicator (``ncclCommCount``), None without one."""
@@ -474,6 +486,11 @@ class DataParallelPipeline:
         strm = list(streams) if streams is not None else \
             [(self.ctx.rank * self.S + i % self.S) if nb == B else (i // B) * self.S + i % self.S
              for i in range(nb)]
+        if self.track:
+            if streams is None:  # the layout's own order, not round-robin
+                strm = [self.ctx.rank * self.S + s for s in self.engine.track_layout(B)]
+            if self.cuda and self.engine._use_device_post():
+                self.engine.check_track_streams(strm, B)
         if scatter and self.ctx.is_root and len(fids) != nb:
             raise ValueError(f"scatter ingest: rank 0 needs metadata for {nb} frames")
         if scatter and not self.ctx.is_root:
@@ -498,7 +515,8 @@ class DataParallelPipeline:
             if self.mask_cap and self.hub is not None and hasattr(self.hub, "push_masks"):
                 self.hub.push_masks(self.engine.host_masks(labels), self._node_meta(fids, strm, tss))
             if self.region_cap and self.hub is not None and hasattr(self.hub, "push_regions"):
-                self.hub.push_regions(self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None)),
+                self.hub.push_regions(self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None),
+                                                               *([strm] if self.track else [])),
                                       self._node_meta(fids, strm, tss), **self._region_kw)
             return self.engine.records_from_labels(labels, fids, tss, strm)
         # the run words of this step's label maps: produced with the records (same graph,

@@ -242,6 +242,10 @@ def serve_distributed(cfg: Config) -> int:
         raise ValueError("--serve_masks is not supported by the multi-rank server (label masks "
                          "are not gathered across ranks); run one GPU, or the supervised "
                          "server (--gpus N without --no_supervise)")
+    if cfg.track_regions and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or cfg.gpus > 1):
+        raise ValueError("--track_regions is not supported by the multi-rank server (class regions "
+                         "and their tracks are not gathered across ranks); run one GPU, or the "
+                         "supervised server (--gpus N without --no_supervise)")
     if cfg.serve_regions and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or cfg.gpus > 1):
         raise ValueError("--serve_regions is not supported by the multi-rank server (class regions "
                          "are not gathered across ranks); run one GPU, or the supervised "

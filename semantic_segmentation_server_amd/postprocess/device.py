@@ -20,12 +20,24 @@ from ..runtime.results import RECORD_DTYPE
 class DevicePostprocess:
     def __init__(self, device: torch.device, H: int, W: int, palette: np.ndarray, K: int = 64,
                  bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
-                 region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False):
+                 region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False,
+                 track_streams: int = 0, track_q: int = 0):
         self.device = device
         # region_conf (--serve_confidence): run() takes the confidence plane beside the labels
         # and the region records have 7 words (sum_conf)
         self.region_conf = bool(region_conf)
         self.region_words = 7 if self.region_conf else 6
+        # track_streams (--track_regions): the number of streams whose frames this object sees,
+        # each batch of B frames laid out by feeder.split_batch(B, track_streams). The region
+        # kernels then write their 6- / 7-word rows to a buffer of their own and the tracking
+        # kernels (hip_ops.region_tracks) the served rows, two words wider. 0: no launch, no
+        # buffer. The streams' carried state is shared by every batch size and every graph.
+        self.track_streams, self.track_q = int(track_streams), int(track_q)
+        if self.track_streams and not region_cap:
+            raise ValueError("DevicePostprocess: track_streams needs region_cap")
+        self.out_words = self.region_words + (2 if self.track_streams else 0)
+        self._track_bufs: Dict[tuple, tuple] = {}
+        self._track_state: Dict[tuple, torch.Tensor] = {}
         # records per frame of the class-region kernels (class_regions.hip); 0: no kernel, no
         # buffer, no launch. region_classes: the served 256-bit class set
         self.region_cap = int(region_cap)
@@ -93,6 +105,38 @@ class DevicePostprocess:
             self._region_bufs[key] = (ws, words)
         return self._region_bufs[key]
 
+    def track_counts(self, B: int):
+        """The rows of a batch of B frames that each stream owns (consecutive, in stream order)."""
+        from ..runtime.feeder import split_batch
+        return split_batch(B, self.track_streams)
+
+    def track_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(scratch, layout tables, [B, 4 + (6 | 7 + 2) region_cap] int32 rows with tracks, the
+        streams' carried state) of the tracking kernels; the state belongs to the crop alone."""
+        key = (B, crop_w, crop_h)
+        if key not in self._track_bufs:
+            tws = torch.zeros(hip_ops.region_tracks_workspace_bytes(B, crop_h, crop_w, self.region_cap),
+                              dtype=torch.uint8, device=self.device)
+            tables = hip_ops.region_track_tables(self.track_counts(B), self.device)
+            wide = torch.zeros((B, 4 + self.out_words * self.region_cap), dtype=torch.int32,
+                               device=self.device)
+            self._track_bufs[key] = (tws, tables, wide)
+        skey = (crop_w, crop_h)
+        if skey not in self._track_state:
+            self._track_state[skey] = torch.zeros(
+                hip_ops.region_tracks_state_bytes(self.track_streams, crop_h, crop_w),
+                dtype=torch.uint8, device=self.device)
+        return self._track_bufs[key] + (self._track_state[skey],)
+
+    def reset_tracks(self) -> None:
+        """Forget every stream's carried state (ids start again at 1), once the device is idle."""
+        if not self._track_state:
+            return
+        torch.cuda.synchronize(self.device)
+        for st in self._track_state.values():
+            st.zero_()
+        torch.cuda.synchronize(self.device)
+
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
             out: torch.Tensor = None, mask_out: torch.Tensor = None,
             region_out: torch.Tensor = None, conf: torch.Tensor = None) -> torch.Tensor:
@@ -105,7 +149,8 @@ class DevicePostprocess:
         follow on the same stream, into ``region_buffers(B)`` or ``region_out`` ([B, 4 + 6
         region_cap] int32 rows); ``last_regions`` is the buffer written. With ``region_conf``,
         ``conf`` is the [B, H, W] uint8 confidence plane of ``labels`` and the rows are [B, 4 + 7
-        region_cap]."""
+        region_cap]. With ``track_streams`` the rows are two words wider (track_id, age) and
+        the frames of ``labels`` are the next ones of their streams, laid out by ``track_counts``."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -127,7 +172,7 @@ class DevicePostprocess:
             self.last_mask = words
         if self.region_cap:
             rws, words = self.region_buffers(B, crop_w, crop_h)
-            if region_out is not None:
+            if region_out is not None and not self.track_streams:
                 words = region_out
             if self.region_conf and conf is None:
                 raise ValueError("DevicePostprocess.run: region_conf needs the conf plane")
@@ -135,6 +180,14 @@ class DevicePostprocess:
                                   crop_w=crop_w, classes=self.region_classes,
                                   min_pixels=self.region_min_pixels, K=self.region_cap,
                                   conf=conf if self.region_conf else None)
+            if self.track_streams:  # same stream, same graph: the rows with track_id and age
+                tws, tables, wide, state = self.track_buffers(B, crop_w, crop_h)
+                if region_out is not None:
+                    wide = region_out
+                hip_ops.region_tracks(words, wide, rws, tws, state, tables,
+                                      counts=self.track_counts(B), crop_h=crop_h, crop_w=crop_w,
+                                      K=self.region_cap, q=self.track_q, conf=self.region_conf)
+                words = wide
             self.last_regions = words
         return rec
 

@@ -32,6 +32,10 @@ region has a seventh word, ``6  sum_conf``: the exact integer sum of the codes o
 ``uint32[4 + 7 * K]`` with the same header. The mean confidence of a region is
 ``sum_conf / (255 * pixels)``.
 
+With region tracks (``--track_regions``, postprocess/tracks.py) two more words follow the others
+of a record, ``track_id`` and ``age`` (at 6 and 7, or at 7 and 8 with ``sum_conf``), and a frame
+is ``uint32[4 + (6 | 7 + 2) * K]`` with the same header.
+
 This module is the oracle of the device kernels (``csrc/hip/class_regions.hip``), the encoder
 of the CPU / torch / exact paths, and the decoder of the RPC.
 """
@@ -44,6 +48,7 @@ import numpy as np
 HEADER = 4
 WORDS = 6                      # per region
 WORDS_CONF = 7                 # per region with sum_conf
+WORDS_TRACK = 2                # more per region with track_id, age
 MAX_PIXELS = 1 << 24           # a root is stored in 24 bits
 MAX_REGIONS = 256              # K
 REGION_CANDIDATES = 4096       # most regions that may pass in a frame (the kernel file's constant)
@@ -51,11 +56,12 @@ REGION_CANDIDATES = 4096       # most regions that may pass in a frame (the kern
 REGION_DTYPE = np.dtype([("label", np.uint8), ("root", np.uint32), ("pixels", np.uint32),
                          ("sum_x", np.uint32), ("sum_y", np.uint32),
                          ("x_min", np.uint16), ("y_min", np.uint16),
-                         ("x_max", np.uint16), ("y_max", np.uint16), ("sum_conf", np.uint32)])
+                         ("x_max", np.uint16), ("y_max", np.uint16), ("sum_conf", np.uint32),
+                         ("track_id", np.uint32), ("age", np.uint32)])
 
 
-def words_per_region(conf: bool = False) -> int:
-    return WORDS_CONF if conf else WORDS
+def words_per_region(conf: bool = False, tracks: bool = False) -> int:
+    return (WORDS_CONF if conf else WORDS) + (WORDS_TRACK if tracks else 0)
 
 Classes = Union[int, Iterable[int]]
 
@@ -144,13 +150,21 @@ def label_components(labels: np.ndarray, mask: int) -> np.ndarray:
 def region_table(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes,
                  min_pixels: int = 1, conf: Optional[np.ndarray] = None) -> np.ndarray:
     """REGION_DTYPE[n]: every passing region of the crop, in the output order. ``sum_conf``
-    is summed from ``conf`` (a uint8 map beside ``labels``) and 0 without it."""
+    is summed from ``conf`` (a uint8 map beside ``labels``) and 0 without it; ``track_id`` and
+    ``age`` are 0 (postprocess/tracks.py fills them)."""
+    return table_and_roots(labels, crop_w, crop_h, classes, min_pixels, conf)[0]
+
+
+def table_and_roots(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes,
+                    min_pixels: int = 1, conf: Optional[np.ndarray] = None):
+    """(``region_table``, int64[crop_h * crop_w]: per pixel the root of its region, -1 outside
+    the class set)."""
     lab = np.ascontiguousarray(np.asarray(labels)[:crop_h, :crop_w])
     roots = label_components(lab, class_mask(classes)).reshape(-1)
     on = np.flatnonzero(roots >= 0)
     out = np.zeros(0, REGION_DTYPE)
     if on.size == 0:
-        return out
+        return out, roots
     r = roots[on]
     order = np.argsort(r, kind="stable")
     on, r = on[order], r[order]
@@ -169,14 +183,17 @@ def region_table(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes,
         c = np.ascontiguousarray(np.asarray(conf)[:crop_h, :crop_w]).reshape(-1).astype(np.int64)
         tab["sum_conf"] = np.add.reduceat(c[on], first)
     tab = tab[keep]
-    return tab[np.lexsort((tab["root"], -tab["pixels"].astype(np.int64)))]
+    return tab[np.lexsort((tab["root"], -tab["pixels"].astype(np.int64)))], roots
 
 
-def pack(tab: np.ndarray, conf: bool = False) -> np.ndarray:
-    """REGION_DTYPE[n] -> uint32[n, 6] record words ([n, 7] with ``conf``)."""
-    w = np.zeros((len(tab), words_per_region(conf)), np.uint32)
+def pack(tab: np.ndarray, conf: bool = False, tracks: bool = False) -> np.ndarray:
+    """REGION_DTYPE[n] -> uint32[n, 6] record words ([n, 7] with ``conf``; two more, track_id
+    and age, with ``tracks``)."""
+    w = np.zeros((len(tab), words_per_region(conf, tracks)), np.uint32)
     if conf:
         w[:, 6] = tab["sum_conf"]
+    if tracks:
+        w[:, -2], w[:, -1] = tab["track_id"], tab["age"]
     w[:, 0] = (tab["label"].astype(np.uint32) << 24) | tab["root"]
     w[:, 1], w[:, 2], w[:, 3] = tab["pixels"], tab["sum_x"], tab["sum_y"]
     w[:, 4] = tab["x_min"].astype(np.uint32) | (tab["y_min"].astype(np.uint32) << 16)
@@ -185,10 +202,12 @@ def pack(tab: np.ndarray, conf: bool = False) -> np.ndarray:
 
 
 def encode(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes, min_pixels: int,
-           K: int, out: Optional[np.ndarray] = None, conf: Optional[np.ndarray] = None) -> np.ndarray:
+           K: int, out: Optional[np.ndarray] = None, conf: Optional[np.ndarray] = None,
+           tracker=None) -> np.ndarray:
     """``labels[H, W]`` uint8 -> ``uint32[4 + 6 K]``; with ``conf[H, W]`` uint8, the
     7-word records: ``uint32[4 + 7 K]``. Unwritten words keep ``out``'s values (zero without
-    ``out``)."""
+    ``out``). With ``tracker`` (a ``tracks.StreamTracker``: the state of this frame's stream,
+    advanced by this call) the records end in ``track_id`` and ``age``."""
     labels = np.asarray(labels)
     if labels.ndim != 2 or labels.dtype != np.uint8:
         raise ValueError("regions.encode: labels must be a 2-D uint8 map")
@@ -196,7 +215,7 @@ def encode(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes, min_p
     if crop_h > labels.shape[0] or crop_w > labels.shape[1]:
         raise ValueError(f"regions.encode: crop {crop_h} x {crop_w} outside the "
                          f"{labels.shape[0]} x {labels.shape[1]} map")
-    rw = words_per_region(conf is not None)
+    rw = words_per_region(conf is not None, tracker is not None)
     if conf is not None:
         conf = np.asarray(conf)
         if conf.shape != labels.shape or conf.dtype != np.uint8:
@@ -205,26 +224,32 @@ def encode(labels: np.ndarray, crop_w: int, crop_h: int, classes: Classes, min_p
         out = np.zeros(HEADER + rw * K, np.uint32)
     elif out.shape != (HEADER + rw * K,) or out.dtype != np.uint32:
         raise ValueError(f"regions.encode: out must be uint32[4 + {rw} K]")
-    tab = region_table(labels, crop_w, crop_h, classes, min_pixels, conf)
-    k = min(len(tab), K)
-    out[0], out[1], out[2], out[3] = len(tab), crop_w * crop_h, crop_w, crop_h
-    out[HEADER:HEADER + rw * k] = pack(tab[:k], conf is not None).reshape(-1)
+    tab, roots = table_and_roots(labels, crop_w, crop_h, classes, min_pixels, conf)
+    total, k = len(tab), min(len(tab), K)
+    tab = tab[:k]
+    if tracker is not None:
+        from . import tracks
+        tab["track_id"], tab["age"] = tracker.update(tab, tracks.plane_of(roots, tab))
+    out[0], out[1], out[2], out[3] = total, crop_w * crop_h, crop_w, crop_h
+    out[HEADER:HEADER + rw * k] = pack(tab, conf is not None, tracker is not None).reshape(-1)
     return out
 
 
-def used_words(words: np.ndarray, K: Optional[int] = None, conf: bool = False) -> int:
+def used_words(words: np.ndarray, K: Optional[int] = None, conf: bool = False,
+               tracks: bool = False) -> int:
     """Header + stored records: ``4 + 6 * min(n_regions, K)`` (``K`` defaults to the array's);
-    7-word records with ``conf``."""
-    rw = words_per_region(conf)
+    7-word records with ``conf``, two more words with ``tracks``."""
+    rw = words_per_region(conf, tracks)
     K = (len(words) - HEADER) // rw if K is None else K
     return HEADER + rw * min(int(words[0]), K)
 
 
-def decode(words: np.ndarray, conf: bool = False) -> np.ndarray:
+def decode(words: np.ndarray, conf: bool = False, tracks: bool = False) -> np.ndarray:
     """``uint32[>= 4 + 6 * stored]`` -> REGION_DTYPE[stored], the stored regions in order
     (``stored = min(n_regions, slots of the array)``; ``words[0]`` is the true total). With
-    ``conf`` the records have 7 words; without, ``sum_conf`` is 0."""
-    WORDS = words_per_region(conf)
+    ``conf`` the records have 7 words; without, ``sum_conf`` is 0. With ``tracks`` two more
+    words, ``track_id`` and ``age``; without, both are 0."""
+    WORDS = words_per_region(conf, tracks)
     words = np.asarray(words)
     if words.ndim != 1 or len(words) < HEADER:
         raise ValueError("regions: words must be a 1-D array with the 4 header words")
@@ -241,4 +266,6 @@ def decode(words: np.ndarray, conf: bool = False) -> np.ndarray:
     tab["x_max"], tab["y_max"] = w[:, 5] & np.uint32(0xFFFF), w[:, 5] >> np.uint32(16)
     if conf:
         tab["sum_conf"] = w[:, 6]
+    if tracks:
+        tab["track_id"], tab["age"] = w[:, WORDS - 2], w[:, WORDS - 1]
     return tab

@@ -1,6 +1,8 @@
 """Captured steps of the engine, one class per capture form: the hipGraphs of one frame buffer
 and the static outputs they write (``labels``; ``post``: packed records or None; ``mask``:
---serve_masks run words or None; ``regions``: --serve_regions region words or None; ``conf``: the
+--serve_masks run words or None; ``regions``: --serve_regions region words or None (two words a
+record wider with --track_regions, whose per-stream state lives in the engine's one
+DevicePostprocess: the post-processing graphs of all slots advance it in replay order); ``conf``: the
 --serve_confidence plane of ``labels``, which the post-processing graph reads, or None).
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
 may be refilled (None: the model ran on the caller's stream).

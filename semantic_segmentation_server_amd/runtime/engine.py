@@ -146,6 +146,23 @@ class Engine:
             raise ValueError("--serve_confidence requires --serve_regions")
         self.region_words = 7 if self.serve_confidence else 6
         self.conf_plane: Optional[torch.Tensor] = None
+        # --track_regions: every stored region record ends in track_id and age
+        # (postprocess/tracks.py), so region_words is two more. On the device the state of the
+        # track_streams streams lives in the one DevicePostprocess, and a batch of B frames is
+        # laid out by feeder.split_batch(B, track_streams); the host paths keep a StreamTracker
+        # per stream id
+        self.track_regions = bool(getattr(cfg, "track_regions", False))
+        self.track_streams = max(1, int(cfg.streams)) if self.track_regions else 0
+        self.track_q = 0
+        self._trackers = None
+        self._track_ids: Dict[int, int] = {}  # layout position of a stream -> its id
+        if self.track_regions:
+            if not cfg.serve_regions:
+                raise ValueError("--track_regions requires --serve_regions")
+            from ..postprocess import tracks as TK
+            self.track_q = TK.quantize(cfg.track_min_overlap)
+            self._trackers = TK.Trackers(self.track_q)
+            self.region_words += 2
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -281,7 +298,8 @@ class Engine:
                                                mask_cap=self.mask_cap, region_cap=self.region_cap,
                                                region_classes=self.region_mask,
                                                region_min_pixels=self.region_min_pixels,
-                                               region_conf=self.serve_confidence)
+                                               region_conf=self.serve_confidence,
+                                               track_streams=self.track_streams, track_q=self.track_q)
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
                                  mask_out=mask_out, region_out=region_out, conf=conf)
         return (rec, self._hip_post.last_mask if self.mask_cap else None,
@@ -300,12 +318,49 @@ class Engine:
             MR.encode(lab[b], self.crop_w, self.crop_h, self.mask_cap, out=out[b])
         return out
 
-    def host_regions(self, labels, conf=None) -> np.ndarray:
+    def track_layout(self, B: int) -> List[int]:
+        """With ``track_regions``: the position (0 .. track_streams - 1) of the stream that owns
+        each row of a batch of B frames -- consecutive rows per stream, feeder.split_batch."""
+        from .feeder import split_batch
+        return [s for s, n in enumerate(split_batch(B, self.track_streams)) for _ in range(n)]
+
+    def check_track_streams(self, streams, B: int) -> None:
+        """With ``track_regions`` on the device: raise unless the ``streams`` of a batch follow
+        the layout the tracking kernels were built for, with the same stream ids as before."""
+        if not self.track_regions:
+            return
+        got, want = _per_frame(streams, B), self.track_layout(B)
+        ids = dict(self._track_ids)
+        ok = len(got) == B and all(ids.setdefault(pos, st) == st for pos, st in zip(want, got))
+        if not ok or len(set(ids.values())) != len(ids):
+            raise ValueError(f"--track_regions: the streams {got} of a batch of {B} frames do not follow "
+                             f"the layout {want} of --streams {self.track_streams} (consecutive rows "
+                             f"per stream, the same streams every step; so far {self._track_ids})")
+        self._track_ids = ids
+
+    def reset_tracks(self) -> None:
+        """Forget the tracks of every stream: the next frame's regions are all new, from id 1.
+        Called after warm-up and capture (their steps advance the state) and when a producer
+        or pipeline starts. Waits for the device."""
+        if not self.track_regions:
+            return
+        self._trackers.reset()
+        self._track_ids = {}
+        if self._hip_post is not None:
+            self._hip_post.reset_tracks()
+
+    def host_regions(self, labels, conf=None, streams=None) -> np.ndarray:
         """uint32 [B, 4 + 6 cap] region words of host label maps by the numpy definition
         (postprocess/regions.py): the CPU path, and a GPU without device post-processing. With
-        ``serve_confidence``, ``conf`` is their confidence plane and the rows are [B, 4 + 7 cap]."""
+        ``serve_confidence``, ``conf`` is their confidence plane and the rows are [B, 4 + 7 cap].
+        With ``track_regions`` two more words a record: the frames advance the StreamTracker of
+        their ``streams`` (default: the layout positions of ``track_layout``), in row order."""
         from ..postprocess import regions as RG
         lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        kw = [{}] * lab.shape[0]
+        if self.track_regions:
+            streams = self.track_layout(lab.shape[0]) if streams is None else _per_frame(streams, lab.shape[0])
+            kw = [{"tracker": self._trackers.of(s)} for s in streams]
         if self.serve_confidence:
             if conf is None:
                 raise ValueError("host_regions: serve_confidence needs the conf plane")
@@ -315,7 +370,7 @@ class Engine:
         out = np.zeros((lab.shape[0], 4 + self.region_words * self.region_cap), np.uint32)
         for b in range(lab.shape[0]):
             RG.encode(lab[b], self.crop_w, self.crop_h, self.region_mask, self.region_min_pixels,
-                      self.region_cap, out=out[b], conf=None if conf is None else conf[b])
+                      self.region_cap, out=out[b], conf=None if conf is None else conf[b], **kw[b])
         return out
 
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
@@ -387,6 +442,9 @@ class Engine:
         # 24.0k for one graph (profiles/r2_parts_ab.txt); slot-parallel (default, below)
         # measured faster still, so parts are off unless asked for.
         self.model_parts = int(os.environ.get("SSA_MODEL_PARTS", "1"))
+        if self.track_regions and self.model_parts > 1:
+            raise ValueError("--track_regions is not supported with SSA_MODEL_PARTS > 1: the parts of "
+                             "a batch are post-processed separately, not as one batch in stream order")
         self.model_streams = []
         self._bound = {b.data_ptr(): b for b in bufs}
         self._slot_of = {b.data_ptr(): i for i, b in enumerate(bufs)}
@@ -424,6 +482,7 @@ class Engine:
         step = self._bound_graphs.get(key)
         if step is None:
             step = self._bound_graphs[key] = capture(self, b, slot=self._slot_of[key])
+            self.reset_tracks()  # the warm-up steps of the capture advanced them
         return step
 
     def preferred_lag(self) -> int:
@@ -464,6 +523,7 @@ class Engine:
                 buf = torch.zeros((B, self.cam[1], self.cam[0], self.frame_channels), dtype=torch.uint8,
                                   device=self.device)
                 step = self._static_step = capture(self, buf)
+                self.reset_tracks()  # the warm-up steps of the capture advanced them
             step.frames.copy_(frames, non_blocking=True)
         step.replay()
         # written by the replay, like the records; and when the frame buffer may be refilled
@@ -524,9 +584,11 @@ class Engine:
             if self.mask_cap:
                 self.masks = self.host_masks(labels)
             if self.region_cap:
-                self.regions = self.host_regions(labels, self.conf_plane)
+                self.regions = self.host_regions(labels, self.conf_plane, streams)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
+        if self._use_device_post():
+            self.check_track_streams(streams, len(frame_ids))
         with torch.cuda.stream(self.stream):
             with tr.stage("h2d", self.stream):
                 frames = torch.from_numpy(np.ascontiguousarray(frames_host)).pin_memory() \
@@ -547,7 +609,7 @@ class Engine:
         if self.mask_cap and post is None:
             self.masks = self.host_masks(labels)
         if self.region_cap and post is None:
-            self.regions = self.host_regions(labels, self.conf_plane)
+            self.regions = self.host_regions(labels, self.conf_plane, streams)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

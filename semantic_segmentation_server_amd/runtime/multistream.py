@@ -27,6 +27,9 @@ class StreamGroup:
                  model: Optional[torch.nn.Module] = None):
         if streams < 1:
             raise ValueError("streams >= 1")
+        if getattr(cfg, "track_regions", False):
+            raise ValueError("--track_regions is not supported by StreamGroup: its engines post-process "
+                             "their streams with separate states; use one engine with --streams")
         self.cfg = cfg
         self.device = device
         self.is_cuda = device.type == "cuda"

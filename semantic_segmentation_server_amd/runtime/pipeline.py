@@ -127,6 +127,8 @@ class Producer(threading.Thread):
     def run(self) -> None:
         failures = 0
         self.hub_clear()
+        if getattr(self.engine, "track_regions", False):  # a producer starts: ids from 1
+            self.engine.reset_tracks()
         if self._use_driver():
             self._run_driver()
             return
@@ -149,6 +151,8 @@ class Producer(threading.Thread):
                     regions = getattr(self.engine, "regions", None)
                     if regions is not None and hasattr(self.hub, "push_regions"):  # --serve_regions
                         kw = {"conf": True} if getattr(self.engine, "serve_confidence", False) else {}
+                        if getattr(self.engine, "track_regions", False):
+                            kw["tracks"] = True
                         self.hub.push_regions(regions, np.array([ids, streams, ts], np.float64).T, **kw)
                 self.metrics.observe("objects_per_frame", len(recs) / max(1, len(ids)))
                 self.metrics.observe("buffer_depth", self.hub.depth)

@@ -143,6 +143,7 @@ class StoredRegions(NamedTuple):
     ts: float
     words: np.ndarray  # uint32[4 + 6 * stored regions] (postprocess/regions.py); 7 with conf
     conf: bool = False  # the records have the seventh word, sum_conf (--serve_confidence)
+    tracks: bool = False  # the records end in track_id and age (--track_regions)
 
 
 def latest_rows(rows: np.ndarray, meta: np.ndarray, unit: int = 1):
@@ -229,20 +230,23 @@ class ResultHub:
 
     # ---- class regions (--serve_regions): the LATEST region words per stream
     def put_regions(self, stream: int, frame_id: int, ts: float, words: np.ndarray,
-                    conf: bool = False) -> None:
+                    conf: bool = False, tracks: bool = False) -> None:
         """Store a COPY of ``words`` (header + stored records, postprocess/regions.py) as the
-        stream's latest regions. ``conf``: the records have 7 words (``sum_conf``)."""
+        stream's latest regions. ``conf``: the records have 7 words (``sum_conf``); ``tracks``:
+        two more, ``track_id`` and ``age``."""
         r = StoredRegions(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True),
-                          bool(conf))
+                          bool(conf), bool(tracks))
         with self._lock:
             self._regions[int(stream)] = r
 
-    def push_regions(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False) -> None:
+    def push_regions(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False,
+                     tracks: bool = False) -> None:
         """As ``push_masks`` for [F, 4 + 6 K] region words: of several frames of one stream
         only the last is copied, and only its ``4 + 6 * min(n_regions, K)`` used words. With
-        ``conf`` the rows are [F, 4 + 7 K] (``sum_conf``), and stored as such."""
-        for st, fid, ts, words in latest_rows(rows, meta, 7 if conf else 6):
-            self.put_regions(st, fid, ts, words, conf)
+        ``conf`` the rows are [F, 4 + 7 K] (``sum_conf``), with ``tracks`` two words a record
+        wider (``track_id``, ``age``), and stored as such."""
+        for st, fid, ts, words in latest_rows(rows, meta, (7 if conf else 6) + (2 if tracks else 0)):
+            self.put_regions(st, fid, ts, words, conf, tracks)
 
     def regions(self, stream: int) -> Optional["StoredRegions"]:
         """The stream's latest regions (frame_id, ts, words), or None before the first ones."""

@@ -175,7 +175,8 @@ class _RecordRing:
 class _WordChannel:
     """The latest row of words per stream -- a 4-word header whose word 0 counts the entries,
     then ``unit`` words per entry: a label mask (postprocess/mask_rle.py run words, unit 1) or
-    a frame's class regions (postprocess/regions.py, unit 6, or 7 with confidence) -- in POSIX
+    a frame's class regions (postprocess/regions.py, unit 6, or 7 with confidence, two more with
+    tracks) -- in POSIX
     shared memory, single writer (the worker) / single reader (the parent).
 
     Block header (int64): 0 streams, 1 cap (entries), 2 first (global) stream id, 3 unit. Per
@@ -299,9 +300,10 @@ class _RingHub:
         for st, fid, ts, words in latest_rows(rows, meta):
             self.masks.write(st, fid, ts, words)
 
-    def push_regions(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False) -> None:
-        """As ResultHub.push_regions; the channel's unit (6, or 7 with confidence: both from the
-        one config) is the rows'."""
+    def push_regions(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False,
+                     tracks: bool = False) -> None:
+        """As ResultHub.push_regions; the channel's unit (6, 7 with confidence, two more with
+        tracks: all from the one config) is the rows'."""
         if self.region_ch is None:
             return
         for st, fid, ts, words in latest_rows(rows, meta, self.region_ch.unit):
@@ -491,7 +493,8 @@ class SupervisedServer:
         w.masks = _WordChannel(self.S, int(self.cfg.mask_max_runs), w.rank * self.S) \
             if self.cfg.serve_masks else None
         w.regions = _WordChannel(self.S, int(self.cfg.max_regions), w.rank * self.S,
-                                 unit=7 if self.cfg.serve_confidence else 6) \
+                                 unit=(7 if self.cfg.serve_confidence else 6)
+                                 + (2 if getattr(self.cfg, "track_regions", False) else 0)) \
             if self.cfg.serve_regions else None
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
@@ -533,7 +536,9 @@ class SupervisedServer:
                 self.hub.put_mask(stream, fid, ts, words)
         if w.regions is not None:
             for stream, fid, ts, words in w.regions.pull():
-                self.hub.put_regions(stream, fid, ts, words, conf=w.regions.unit == 7)
+                # unit 6, 7 (confidence), 8 (tracks) or 9 (both)
+                self.hub.put_regions(stream, fid, ts, words, conf=w.regions.unit in (7, 9),
+                                     tracks=w.regions.unit in (8, 9))
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
