@@ -663,7 +663,7 @@ def test_device_postprocess_matches_spec(seed, h, w, min_area, post_accum):
         for j in range(n):
             lab, score, area, cx, cy = exp[j][:5]
             assert int(got[j, 0]) == lab
-            assert abs(got[j, 1] - score) < 1e-6
+            assert got[j, 1] == np.float32(score)
             assert got[j, 2] == np.float32(min(1.0, area / (W * H)))
             assert got[j, 3] == np.float32(min(1.0, cx / W))
             assert got[j, 4] == np.float32(min(1.0, cy / H))
@@ -697,7 +697,7 @@ def test_device_postprocess_many_components(block, period, min_area, post_accum)
         got = rec[i, 1:1 + 5 * n].reshape(n, 5)
         for j in range(n):
             lab_, score, area, cx, cy = exp[j][:5]
-            assert int(got[j, 0]) == lab_ and abs(got[j, 1] - score) < 1e-6
+            assert int(got[j, 0]) == lab_ and got[j, 1] == np.float32(score)
             assert got[j, 2] == np.float32(min(1.0, area / (w * h)))
             assert got[j, 3] == np.float32(min(1.0, cx / w))
             assert got[j, 4] == np.float32(min(1.0, cy / h))
@@ -732,7 +732,7 @@ def test_device_postprocess_pool_exhausted():
             assert n == len(exp), (i, n, len(exp))
             got = rec[i, 1:1 + 5 * n].reshape(n, 5)
             for j in range(n):
-                assert int(got[j, 0]) == exp[j][0] and abs(got[j, 1] - exp[j][1]) < 1e-6
+                assert int(got[j, 0]) == exp[j][0] and got[j, 1] == np.float32(exp[j][1])
                 assert got[j, 3] == np.float32(min(1.0, exp[j][3] / w))
     assert lost[0] == lost[1]
 
@@ -763,7 +763,7 @@ def test_device_postprocess_two_lattice_frames_fit():
         assert n == len(exp), (i, n, len(exp))
         got = rec[i, 1:1 + 5 * n].reshape(n, 5)
         for j in range(n):
-            assert int(got[j, 0]) == exp[j][0] and abs(got[j, 1] - exp[j][1]) < 1e-6
+            assert int(got[j, 0]) == exp[j][0] and got[j, 1] == np.float32(exp[j][1])
 
 
 @pytest.mark.parametrize("K", [8, 64])
@@ -798,7 +798,7 @@ def test_device_postprocess_overflow_deterministic(K, post_accum):
         got = rec[i, 1:1 + 5 * K].reshape(K, 5)
         for j in range(K):
             lab_, score, area, cx, cy = exp[j][:5]
-            assert int(got[j, 0]) == lab_ and abs(got[j, 1] - score) < 1e-6
+            assert int(got[j, 0]) == lab_ and got[j, 1] == np.float32(score)
             assert got[j, 3] == np.float32(min(1.0, cx / w)) and got[j, 4] == np.float32(min(1.0, cy / h))
     assert rec[2, 0] == 0
 
@@ -824,7 +824,7 @@ def test_device_postprocess_deep_nesting(post_accum):
     got = rec[0, 1:1 + 5 * n].reshape(n, 5)
     for j in range(n):
         lab_, score, area, cx, cy = exp[j][:5]
-        assert int(got[j, 0]) == lab_ and abs(got[j, 1] - score) < 1e-6, j
+        assert int(got[j, 0]) == lab_ and got[j, 1] == np.float32(score), j
         assert got[j, 2] == np.float32(min(1.0, area / (w * h))), j
 
 
