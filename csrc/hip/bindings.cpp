@@ -499,6 +499,23 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("crop_h"), py::arg("crop_w"), py::arg("K"), py::arg("record_words"), py::arg("q"),
         py::arg("stream"), py::arg("kernels") = 31);
 
+  m.def("zone_stats_workspace_bytes", &zone_stats_workspace_bytes, py::arg("B"), py::arg("R"),
+        py::arg("C"), py::arg("conf") = false);
+  m.def("zone_stats",
+        [](uintptr_t labels, uintptr_t conf, uintptr_t plane, int B, int H, int W, int crop_h,
+           int crop_w, int R, int C, uintptr_t out, uintptr_t ws, uintptr_t stream) {
+          ZoneStatsParams p;
+          p.labels = P<const uint8_t>(labels); p.conf = P<const uint8_t>(conf);
+          p.plane = P<const uint32_t>(plane);
+          p.B = B; p.H = H; p.W = W; p.crop_h = crop_h; p.crop_w = crop_w; p.R = R; p.C = C;
+          p.out = P<uint32_t>(out); p.ws = P<uint32_t>(ws);
+          zone_stats(p, S(stream));
+        },
+        py::arg("labels"), py::arg("conf"), py::arg("plane"), py::arg("B"), py::arg("H"),
+        py::arg("W"), py::arg("crop_h"), py::arg("crop_w"), py::arg("R"), py::arg("C"),
+        py::arg("out"), py::arg("ws"), py::arg("stream"));
+  m.attr("ZONE_STATS_CHUNK") = zone_stats_chunk();
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

@@ -403,4 +403,23 @@ size_t region_tracks_workspace_bytes(int B, int crop_h, int crop_w, int K);
 size_t region_tracks_state_bytes(int streams, int crop_h, int crop_w);
 void region_tracks(const RegionTracksParams& p, hipStream_t s);
 
+// ---- zone occupancy (zone_stats.hip; the definition is postprocess/zones.py) -----------------
+// Per frame, over the flat crop labels[:crop_h, :crop_w] (N = crop_h * crop_w < 2^24 pixels):
+// out[b] = uint32[4 + R C] = R, N, crop_w, crop_h, then pixels[r][c], the number of pixels of
+// class c < C whose bit r - 1 is set in plane (row 0: every pixel). With `conf` a second [R][C]
+// block follows, sum_conf: the exact sum of the codes of the same pixels (out is [B, 4 + 2 R C]).
+// Labels >= C count nowhere. 1 <= R <= 33, 1 <= C <= 256, R * C <= 4096. Every word of out is
+// written by every run.
+struct ZoneStatsParams {
+  const uint8_t* labels = nullptr;   // [B, H, W] (row stride W)
+  const uint8_t* conf = nullptr;     // [B, H, W] or null
+  const uint32_t* plane = nullptr;   // [crop_h, crop_w], or null when R == 1; shared by all frames
+  int B = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, R = 0, C = 0;
+  uint32_t* out = nullptr;           // [B, 4 + R * C * (conf ? 2 : 1)]
+  uint32_t* ws = nullptr;            // zone_stats_workspace_bytes(B, R, C, conf): 0 at present
+};
+size_t zone_stats_workspace_bytes(int B, int R, int C, bool conf);
+int zone_stats_chunk();  // flat pixels per workgroup
+void zone_stats(const ZoneStatsParams& p, hipStream_t s);
+
 }  // namespace ssa

@@ -186,6 +186,38 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "has_confidence", 11, F.TYPE_BOOL)  # the regions carry a confidence
     _field(m, "has_tracks", 12, F.TYPE_BOOL)      # the regions carry track_id and age
 
+    m = fd.message_type.add(); m.name = "ZoneRequest"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+
+    # one class present in one zone (postprocess/zones.py); the floats are computed from the
+    # stored integer counts
+    m = fd.message_type.add(); m.name = "ZoneClass"
+    _field(m, "class_id", 1, F.TYPE_INT32)
+    _field(m, "label", 2, F.TYPE_STRING)
+    _field(m, "pixels", 3, F.TYPE_UINT32)
+    _field(m, "share", 4, F.TYPE_FLOAT)       # pixels / the zone's pixels
+    _field(m, "confidence", 5, F.TYPE_FLOAT)  # sum_conf / (255 * pixels); 0 without has_confidence
+
+    m = fd.message_type.add(); m.name = "Zone"
+    _field(m, "index", 1, F.TYPE_INT32)       # 0: the implicit whole-frame zone "frame"
+    _field(m, "name", 2, F.TYPE_STRING)
+    _field(m, "pixels", 3, F.TYPE_UINT32)     # the sum over the classes: zone within the crop
+    _field(m, "area", 4, F.TYPE_FLOAT)        # pixels / (width * height)
+    # the classes with pixels > 0, by (pixels descending, class_id ascending)
+    _field(m, "classes", 5, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "ZoneClass")
+
+    # the class x zone pixel counts of the stream's latest frame
+    m = fd.message_type.add(); m.name = "ZoneOccupancy"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "frame_id", 2, F.TYPE_INT64)
+    _field(m, "timestamp", 3, F.TYPE_DOUBLE)
+    _field(m, "width", 4, F.TYPE_INT32)    # crop region, model-resolution pixels
+    _field(m, "height", 5, F.TYPE_INT32)
+    _field(m, "model_width", 6, F.TYPE_INT32)
+    _field(m, "model_height", 7, F.TYPE_INT32)
+    _field(m, "zones", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "Zone")
+    _field(m, "has_confidence", 9, F.TYPE_BOOL)  # the classes carry a confidence
+
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"
     E = ".sem_seg_server.Empty"
@@ -195,6 +227,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _method(svc, "Health", E, P + "HealthStatus")
     _method(svc, "GetSegmentationMask", P + "MaskRequest", P + "SegmentationMask")
     _method(svc, "GetClassRegions", P + "RegionRequest", P + "ClassRegions")
+    _method(svc, "GetZoneOccupancy", P + "ZoneRequest", P + "ZoneOccupancy")
     return fd
 
 
@@ -254,6 +287,10 @@ SegmentationMask = _cls("sem_seg_server.v2.SegmentationMask")
 RegionRequest = _cls("sem_seg_server.v2.RegionRequest")
 ClassRegion = _cls("sem_seg_server.v2.ClassRegion")
 ClassRegions = _cls("sem_seg_server.v2.ClassRegions")
+ZoneRequest = _cls("sem_seg_server.v2.ZoneRequest")
+ZoneClass = _cls("sem_seg_server.v2.ZoneClass")
+Zone = _cls("sem_seg_server.v2.Zone")
+ZoneOccupancy = _cls("sem_seg_server.v2.ZoneOccupancy")
 
 # ---- grpc.health.v1 ---------------------------------------------------------
 HealthCheckRequest = _cls("grpc.health.v1.HealthCheckRequest")
@@ -270,6 +307,7 @@ V2_METHODS = {
     "Health": (Empty, HealthStatus),
     "GetSegmentationMask": (MaskRequest, SegmentationMask),
     "GetClassRegions": (RegionRequest, ClassRegions),
+    "GetZoneOccupancy": (ZoneRequest, ZoneOccupancy),
 }
 
 

@@ -19,6 +19,7 @@ from concurrent import futures
 from typing import Callable, Dict, Optional, Tuple
 
 import grpc
+import numpy as np
 
 from . import proto as P
 from ..labels import label_name
@@ -73,8 +74,10 @@ class SemanticSegmentationV2Servicer:
                  streams: Optional[list] = None, metrics=None,
                  health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None, *,
                  serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0),
-                 serve_regions: bool = False):
+                 serve_regions: bool = False, zone_names: Optional[list] = None):
         self.hub = hub
+        # --serve_zones: the names of the zone rows, "frame" first (None: GetZoneOccupancy is off)
+        self.zone_names = list(zone_names) if zone_names else None
         self.serve_regions = bool(serve_regions)  # --serve_regions: GetClassRegions is enabled
         self.serve_masks = bool(serve_masks)  # --serve_masks: GetSegmentationMask is enabled
         self.model_size = model_size          # (width, height) of the label maps
@@ -167,6 +170,43 @@ class SemanticSegmentationV2Servicer:
             height=int(r.words[3]), model_width=int(self.model_size[0]),
             model_height=int(self.model_size[1]), regions=out, total_regions=total,
             truncated=len(out) < total, has_confidence=has_conf, has_tracks=has_tracks)
+
+    def GetZoneOccupancy(self, request, context):
+        """The pixels of every class inside every zone of the stream's latest frame. The
+        producer stores integer counts (postprocess/zones.py); the floats of the wire format
+        are computed here, for the one stream an RPC asks for."""
+        from ..postprocess import zones as ZN
+        stream = int(request.stream_id)
+        if self.zone_names is None:
+            context.set_code(grpc.StatusCode.FAILED_PRECONDITION)
+            context.set_details("zone occupancy is not enabled (start the server with --serve_zones)")
+            return P.ZoneOccupancy()
+        if self.hub.get(stream) is None:
+            context.set_code(grpc.StatusCode.NOT_FOUND)
+            context.set_details(f"unknown stream_id {request.stream_id}")
+            return P.ZoneOccupancy()
+        z = self.hub.zones(stream)
+        if z is None:
+            context.set_code(grpc.StatusCode.UNAVAILABLE)
+            context.set_details(f"no frame of stream {stream} collected yet")
+            return P.ZoneOccupancy()
+        has_conf = bool(z.conf)
+        st = ZN.decode(z.words, conf=has_conf)
+        out = []
+        for r in range(st.rows):
+            px = st.pixels[r].astype(np.int64)
+            total = int(px.sum())
+            ids = [int(c) for c in np.lexsort((np.arange(len(px)), -px)) if px[c] > 0]
+            classes = [P.ZoneClass(
+                class_id=c, label=label_name(self.labels, c), pixels=int(px[c]),
+                share=int(px[c]) / total,
+                confidence=int(st.sum_conf[r, c]) / (255 * int(px[c])) if has_conf else 0.0) for c in ids]
+            out.append(P.Zone(index=r, name=self.zone_names[r] if r < len(self.zone_names) else str(r),
+                              pixels=total, area=total / st.n if st.n else 0.0, classes=classes))
+        return P.ZoneOccupancy(
+            stream_id=stream, frame_id=z.frame_id, timestamp=z.ts, width=st.crop_w, height=st.crop_h,
+            model_width=int(self.model_size[0]), model_height=int(self.model_size[1]), zones=out,
+            has_confidence=has_conf)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

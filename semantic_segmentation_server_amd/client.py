@@ -112,6 +112,24 @@ def print_regions(m) -> None:
               ("  track {:>5}  age {:>5}".format(r.track_id, r.age) if m.has_tracks else ""))
 
 
+def fetch_zones(target: str, stream: int = 0):
+    """The ZoneOccupancy message of the stream's latest frame (v2 GetZoneOccupancy)."""
+    with grpc.insecure_channel(target) as ch:
+        return SemanticSegmentationV2Stub(ch).GetZoneOccupancy(P.ZoneRequest(stream_id=stream))
+
+
+def print_zones(m) -> None:
+    print("stream {} frame {} ts {:.3f}: {} zones in {} x {} (model {} x {})".format(
+        m.stream_id, m.frame_id, m.timestamp, len(m.zones), m.width, m.height, m.model_width,
+        m.model_height))
+    for z in m.zones:
+        print("  zone {:>2} {:<16} {:>8} px  area {:.4f}".format(z.index, z.name, z.pixels, z.area))
+        for c in z.classes:
+            print("    {:<16} {:>3} {:<20} {:>8} px  share {:.4f}".format(
+                z.name, c.class_id, c.label, c.pixels, c.share) +
+                  ("  conf {:.3f}".format(c.confidence) if m.has_confidence else ""))
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="sem_seg_server example client")
     p.add_argument("--target", default="localhost:50051")
@@ -127,7 +145,19 @@ def main(argv=None) -> int:
     p.add_argument("--regions", nargs="?", type=int, const=0, default=None, metavar="STREAM",
                    help="fetch the class regions of the stream's latest frame (server run with "
                         "--serve_regions) and print one line per region")
+    p.add_argument("--zones_of", nargs="?", type=int, const=0, default=None, metavar="STREAM",
+                   help="fetch the zone occupancy of the stream's latest frame (server run with "
+                        "--serve_zones) and print, per zone, one line per class present")
     a = p.parse_args(argv)
+    if a.zones_of is not None:
+        try:
+            m = fetch_zones(a.target, a.zones_of)
+        except grpc.RpcError as err:
+            print(err.details())
+            print("{}, {}".format(err.code().name, err.code().value))
+            return 1
+        print_zones(m)
+        return 0
     if a.regions is not None:
         try:
             m = fetch_regions(a.target, a.regions)

@@ -70,6 +70,8 @@ class Config:
     serve_confidence: bool = False         # per-pixel confidence on the device, served per class region
     track_regions: bool = False            # match the regions of consecutive frames: track_id, age per region
     track_min_overlap: float = 0.25        # overlap / smaller region that continues a track, in (0, 1]
+    serve_zones: bool = False              # class x zone pixel counts of every label map (v2 GetZoneOccupancy)
+    zones: Optional[str] = None            # zone file (JSON, postprocess/zones.py); None: the frame zone alone
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -91,9 +93,13 @@ class Config:
         if self.pixel_format not in PIXEL_FORMATS:
             raise ValueError(f"--pixel_format must be one of {', '.join(PIXEL_FORMATS)}, "
                              f"got {self.pixel_format!r}")
-        if self.serve_confidence and not self.serve_regions:
-            raise ValueError("--serve_confidence requires --serve_regions: the confidence is served "
-                             "per class region (v2 GetClassRegions)")
+        if self.serve_confidence and not (self.serve_regions or self.serve_zones):
+            raise ValueError("--serve_confidence requires --serve_regions or --serve_zones: the "
+                             "confidence is served per class region (v2 GetClassRegions) or per "
+                             "class and zone (v2 GetZoneOccupancy)")
+        if self.zones and not self.serve_zones:
+            raise ValueError(f"--zones {self.zones} requires --serve_zones: the zones are served by "
+                             "v2 GetZoneOccupancy")
         if self.track_regions and not self.serve_regions:
             raise ValueError("--track_regions requires --serve_regions: a track is the identity of a "
                              "class region across frames (v2 GetClassRegions)")
@@ -190,7 +196,8 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--serve_confidence", action="store_true",
                    help="compute the winning class's softmax probability of every pixel on the "
                         "device and serve its mean per class region (v2 GetClassRegions "
-                        "confidence); requires --serve_regions")
+                        "confidence) and per class and zone (v2 GetZoneOccupancy); requires "
+                        "--serve_regions or --serve_zones")
     p.add_argument("--track_regions", action="store_true",
                    help="match the class regions of each stream's consecutive frames by pixel "
                         "overlap on the device and serve a track id and an age per region (v2 "
@@ -198,6 +205,13 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--track_min_overlap", type=float, default=d.track_min_overlap,
                    help="smallest overlap, as a share of the smaller of two regions, that "
                         "continues a track (0 < ratio <= 1)")
+    p.add_argument("--serve_zones", action="store_true",
+                   help="count the pixels of every class inside every zone of each frame's label "
+                        "map on the device and serve the latest counts per stream (v2 "
+                        "GetZoneOccupancy); zone 0 is the whole frame; one GPU per process group")
+    p.add_argument("--zones", default=d.zones, metavar="FILE.json",
+                   help="zone file: up to 32 named polygons or rectangles in normalised camera "
+                        "coordinates; requires --serve_zones (without it only the frame zone is served)")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

@@ -1399,6 +1399,73 @@ def region_tracks(rows, out, ws, tws, state, tables, *, counts, crop_h, crop_w, 
     return out
 
 
+ZONE_COUNTERS = 4096      # R * C counters of zone_stats' on-chip table (zones.py ZONE_COUNTERS)
+ZONE_MAX_PIXELS = 1 << 24  # 255 * N fits a word
+
+
+def zone_stats_workspace_bytes(B, R, C, conf: bool = False) -> int:
+    return int(_hip_mod().zone_stats_workspace_bytes(int(B), int(R), int(C), bool(conf)))
+
+
+def zone_stats_chunk() -> int:
+    """Flat pixels per workgroup of ``zone_stats`` (the module's ZONE_STATS_CHUNK)."""
+    return int(_hip_mod().ZONE_STATS_CHUNK)
+
+
+def zone_stats(labels, out, ws, *, B, H, W, crop_h, crop_w, R, C, plane=None, conf=None):
+    """Zone occupancy of ``labels[:, :crop_h, :crop_w]`` (csrc/hip/zone_stats.hip; the format is
+    postprocess/zones.py's): per frame ``out[b] = [R, N, crop_w, crop_h, pixels[R][C]]``, the pixels
+    of class ``c < C`` in row ``r`` -- row 0 the whole crop, row ``r`` the pixels whose bit ``r - 1``
+    is set in ``plane`` (uint32/int32 [crop_h, crop_w], shared by the frames; None iff ``R == 1``).
+    With ``conf`` (a uint8 [B, H, W] plane of per-pixel confidence codes) a second block,
+    ``sum_conf[R][C]``, follows: ``out`` is uint32/int32 [B, 4 + R C] or [B, 4 + 2 R C]; ``ws``:
+    uint8, at least ``zone_stats_workspace_bytes``. Every word of ``out`` is written."""
+    from ..postprocess import zones as ZN
+    B, H, W, crop_h, crop_w, R, C = (int(v) for v in (B, H, W, crop_h, crop_w, R, C))
+    _chk(labels, torch.uint8, "labels")
+    if tuple(labels.shape) != (B, H, W):
+        raise ValueError(f"labels: shape {tuple(labels.shape)} != ({B}, {H}, {W})")
+    if B < 1 or B > 65535:
+        raise ValueError(f"zone_stats: bad batch {B}")
+    if not (1 <= crop_h <= H and 1 <= crop_w <= W):
+        raise ValueError(f"zone_stats: crop {crop_h} x {crop_w} outside the {H} x {W} map")
+    if crop_h * crop_w >= ZONE_MAX_PIXELS:
+        raise ValueError(f"zone_stats: {crop_h} x {crop_w} pixels, a confidence sum needs fewer "
+                         f"than {ZONE_MAX_PIXELS}")
+    if not 1 <= R <= 1 + ZN.MAX_ZONES:
+        raise ValueError(f"zone_stats: R {R} outside 1 .. {1 + ZN.MAX_ZONES}")
+    if not 1 <= C <= ZN.MAX_CLASSES:
+        raise ValueError(f"zone_stats: C {C} outside 1 .. {ZN.MAX_CLASSES}")
+    if R * C > ZONE_COUNTERS or ZN.ZONE_COUNTERS != ZONE_COUNTERS or ZN.MAX_PIXELS != ZONE_MAX_PIXELS:
+        raise ValueError(f"zone_stats: R * C = {R * C} counters, at most ZONE_COUNTERS = {ZONE_COUNTERS}")
+    if (plane is None) != (R == 1):
+        raise ValueError(f"zone_stats: R = {R} {'needs a' if R > 1 else 'takes no'} zone plane")
+    if plane is not None:
+        if plane.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"plane: expected uint32 or int32, got {plane.dtype}")
+        _chk(plane, plane.dtype, "plane")
+        if tuple(plane.shape) != (crop_h, crop_w):
+            raise ValueError(f"plane: shape {tuple(plane.shape)} != ({crop_h}, {crop_w})")
+    if conf is not None:
+        _chk(conf, torch.uint8, "conf")
+        if tuple(conf.shape) != (B, H, W):
+            raise ValueError(f"conf: shape {tuple(conf.shape)} != ({B}, {H}, {W})")
+    if out.dtype not in (torch.int32, torch.uint32):
+        raise TypeError(f"out: expected uint32 or int32, got {out.dtype}")
+    _chk(out, out.dtype, "out")
+    nw = 4 + R * C * (2 if conf is not None else 1)
+    if tuple(out.shape) != (B, nw):
+        raise ValueError(f"out: shape {tuple(out.shape)} != ({B}, {nw})")
+    _chk(ws, torch.uint8, "ws", zone_stats_workspace_bytes(B, R, C, conf is not None))
+    for t in (plane, conf, out, ws):
+        if t is not None and t.device != labels.device:
+            raise ValueError("zone_stats: the buffers are on different devices")
+    _hip_mod().zone_stats(_ptr(labels), _ptr(conf), _ptr(plane), B, H, W, crop_h, crop_w, R, C,
+                          _ptr(out), _ptr(ws), _stream())
+    _dbg('zone_stats')
+    return out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

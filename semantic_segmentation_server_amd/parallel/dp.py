@@ -201,6 +201,19 @@ class DataParallelPipeline:
             raise ValueError("serve_regions is not supported in a multi-rank group (world size "
                              f"{ctx.world}): class regions are not gathered across ranks; run one "
                              "GPU, or the supervised server (independent workers)")
+        # --serve_zones: the same for each step's zone words ([B, 4 + R C], [B, 4 + 2 R C] with
+        # confidence), written to pinned memory by the records' copy kernel (_d2h): as a D2H
+        # hipMemcpyAsync the 27 KB of 32 frames x 5 rows with confidence kept the host thread
+        # busy 0.68 ms a step instead of 0.10 ("Zone occupancy")
+        self.zone_rows = int(getattr(engine, "zone_rows", 0) or 0)
+        self.zone_words, self.zone_conf = 0, bool(getattr(engine, "zone_conf", False))
+        if self.zone_rows:
+            from ..postprocess import zones as ZN
+            self.zone_words = ZN.frame_words(self.zone_rows, int(engine.zone_classes), self.zone_conf)
+            if ctx.initialized and ctx.world > 1:
+                raise ValueError("serve_zones is not supported in a multi-rank group (world size "
+                                 f"{ctx.world}): zone occupancy is not gathered across ranks; run one "
+                                 "GPU, or the supervised server (independent workers)")
         # lag L >= 1: step k collects step k-L's records, with L + 1 staging slots (so L + 1
         # steps can be in flight on a slot-parallel engine); SSA_PIPE_LAG overrides a
         # non-zero lag, else the engine may ask for more depth (slot-parallel: 2)
@@ -286,6 +299,9 @@ class DataParallelPipeline:
         self.local_regions = [torch.zeros((self.B, 4 + self.region_words * self.region_cap), dtype=torch.int32,
                                           pin_memory=self.cuda) for _ in range(NS)] \
             if self.region_cap else None
+        self.local_zones = [torch.zeros((self.B, self.zone_words), dtype=torch.int32,
+                                        pin_memory=self.cuda) for _ in range(NS)] \
+            if self.zone_rows else None
         if gather == "host" and ctx.initialized:
             self.host_send = torch.empty((self.B, self.comb_width), dtype=torch.float32)
             self.host_gather = torch.empty((ctx.world, self.B, self.comb_width), dtype=torch.float32)
@@ -518,11 +534,15 @@ class DataParallelPipeline:
                 self.hub.push_regions(self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None),
                                                                *([strm] if self.track else [])),
                                       self._node_meta(fids, strm, tss), **self._region_kw)
+            if self.zone_rows and self.hub is not None and hasattr(self.hub, "push_zones"):
+                self.hub.push_zones(self.engine.host_zones(labels, getattr(self.engine, "conf_plane", None)),
+                                    self._node_meta(fids, strm, tss), conf=self.zone_conf)
             return self.engine.records_from_labels(labels, fids, tss, strm)
         # the run words of this step's label maps: produced with the records (same graph,
         # same stream), copied with them, before the step's event
         mask = self.engine.mask_packed if self.mask_cap else None
         regions = self.engine.region_packed if self.region_cap else None
+        zones = self.engine.zone_packed if self.zone_rows else None
         slot = self._rslot
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
@@ -537,6 +557,8 @@ class DataParallelPipeline:
                         self._d2h_mask(mask, self.local_mask[slot])
                     if regions is not None:
                         self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
+                    if zones is not None:
+                        self._d2h(zones, self.local_zones[slot])
                 ev = self._rec_ev[slot]  # per record slot: collected before the slot is reused
                 ev.record(rs)
             else:
@@ -545,6 +567,8 @@ class DataParallelPipeline:
                     self._d2h_mask(mask, self.local_mask[slot])
                 if regions is not None:
                     self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
+                if zones is not None:
+                    self._d2h(zones, self.local_zones[slot])
                 if self.cuda:
                     ev = self._rec_ev[slot]
                     ev.record(fast_cuda.current_stream(self.dev_index))
@@ -574,6 +598,8 @@ class DataParallelPipeline:
                 self._d2h_mask(mask, self.local_mask[slot])
             if regions is not None:
                 self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
+            if zones is not None:
+                self._d2h(zones, self.local_zones[slot])
             # every rank (non-root ones too) records the step and goes through the lag
             # throttle: meta_host[slot] is rewritten only after the step that last used it
             # has been collected, i.e. after its H2D copy ran (VERDICT r3 Weak #4: non-root
@@ -789,3 +815,9 @@ class DataParallelPipeline:
             self.hub.push_masks(self.local_mask[slot].numpy(), meta)
         if self.region_cap and hasattr(self.hub, "push_regions"):
             self.hub.push_regions(self.local_regions[slot].numpy(), meta, **self._region_kw)
+        self._push_zones(slot, meta)
+
+    def _push_zones(self, slot: int, meta: np.ndarray) -> None:
+        """The same for the collected step's zone words, if the hub takes zones."""
+        if self.zone_rows and hasattr(self.hub, "push_zones"):
+            self.hub.push_zones(self.local_zones[slot].numpy(), meta, conf=self.zone_conf)

@@ -250,6 +250,10 @@ def serve_distributed(cfg: Config) -> int:
         raise ValueError("--serve_regions is not supported by the multi-rank server (class regions "
                          "are not gathered across ranks); run one GPU, or the supervised "
                          "server (--gpus N without --no_supervise)")
+    if getattr(cfg, "serve_zones", False) and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or cfg.gpus > 1):
+        raise ValueError("--serve_zones is not supported by the multi-rank server (zone occupancy "
+                         "is not gathered across ranks); run one GPU, or the supervised "
+                         "server (--gpus N without --no_supervise)")
     from .affinity import pin_to_gpu_numa
     pin_to_gpu_numa()  # before the first GPU call of this process
     srv = DistributedServer(cfg)

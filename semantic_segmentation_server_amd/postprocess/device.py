@@ -21,8 +21,20 @@ class DevicePostprocess:
     def __init__(self, device: torch.device, H: int, W: int, palette: np.ndarray, K: int = 64,
                  bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
                  region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False,
-                 track_streams: int = 0, track_q: int = 0):
+                 track_streams: int = 0, track_q: int = 0, zone_rows: int = 0, zone_classes: int = 0,
+                 zone_conf: bool = False):
         self.device = device
+        # zone_rows (--serve_zones): R = 1 + the user zones of the zone-occupancy kernel
+        # (zone_stats.hip), zone_classes its C; 0: no kernel, no buffer, no launch. zone_conf:
+        # run() takes the confidence plane and the rows have the sum_conf block. The zone plane
+        # (set_zone_plane) belongs to the crop and is shared by every batch size and every graph
+        self.zone_rows, self.zone_classes = int(zone_rows), int(zone_classes)
+        self.zone_conf = bool(zone_conf)
+        if self.zone_rows and not self.zone_classes:
+            raise ValueError("DevicePostprocess: zone_rows needs zone_classes")
+        self._zone_bufs: Dict[tuple, tuple] = {}
+        self._zone_plane: Dict[tuple, torch.Tensor] = {}
+        self.last_zones = None
         # region_conf (--serve_confidence): run() takes the confidence plane beside the labels
         # and the region records have 7 words (sum_conf)
         self.region_conf = bool(region_conf)
@@ -105,6 +117,43 @@ class DevicePostprocess:
             self._region_bufs[key] = (ws, words)
         return self._region_bufs[key]
 
+    def zone_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(workspace, [B, 4 + R C] int32 zone words, [B, 4 + 2 R C] with ``zone_conf``) of the
+        zone-occupancy kernel for a batch of B frames: static and shared like ``mask_buffers``.
+        Every run writes every word."""
+        key = (B, crop_w, crop_h)
+        if key not in self._zone_bufs:
+            from . import zones as ZN
+            ZN.check_geometry(crop_w, crop_h, self.zone_rows - 1, self.zone_classes)
+            ws = torch.zeros(hip_ops.zone_stats_workspace_bytes(B, self.zone_rows, self.zone_classes,
+                                                                self.zone_conf),
+                             dtype=torch.uint8, device=self.device)
+            words = torch.zeros((B, ZN.frame_words(self.zone_rows, self.zone_classes, self.zone_conf)),
+                                dtype=torch.int32, device=self.device)
+            self._zone_bufs[key] = (ws, words)
+        return self._zone_bufs[key]
+
+    def set_zone_plane(self, plane: np.ndarray) -> None:
+        """The rasterised zones of a crop (uint32 [crop_h, crop_w], postprocess/zones.py
+        ``rasterize``), uploaded once; the runs of that crop read it. A plane already set for
+        the crop is overwritten in place (captured graphs keep the address), once the device
+        is idle."""
+        if self.zone_rows < 2:
+            raise ValueError("DevicePostprocess.set_zone_plane: no user zones (zone_rows < 2)")
+        plane = np.ascontiguousarray(plane, np.uint32)
+        if plane.ndim != 2:
+            raise ValueError(f"zone plane: shape {plane.shape} is not (crop_h, crop_w)")
+        if int(plane.max(initial=0)) >> (self.zone_rows - 1):
+            raise ValueError(f"zone plane: bits past the {self.zone_rows - 1} user zones")
+        key = (plane.shape[1], plane.shape[0])
+        t = torch.from_numpy(plane.view(np.int32))
+        if key in self._zone_plane:
+            torch.cuda.synchronize(self.device)
+            self._zone_plane[key].copy_(t)
+            torch.cuda.synchronize(self.device)
+        else:
+            self._zone_plane[key] = t.to(self.device)
+
     def track_counts(self, B: int):
         """The rows of a batch of B frames that each stream owns (consecutive, in stream order)."""
         from ..runtime.feeder import split_batch
@@ -139,7 +188,8 @@ class DevicePostprocess:
 
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
             out: torch.Tensor = None, mask_out: torch.Tensor = None,
-            region_out: torch.Tensor = None, conf: torch.Tensor = None) -> torch.Tensor:
+            region_out: torch.Tensor = None, conf: torch.Tensor = None,
+            zone_out: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
         shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
@@ -150,7 +200,10 @@ class DevicePostprocess:
         region_cap] int32 rows); ``last_regions`` is the buffer written. With ``region_conf``,
         ``conf`` is the [B, H, W] uint8 confidence plane of ``labels`` and the rows are [B, 4 + 7
         region_cap]. With ``track_streams`` the rows are two words wider (track_id, age) and
-        the frames of ``labels`` are the next ones of their streams, laid out by ``track_counts``."""
+        the frames of ``labels`` are the next ones of their streams, laid out by ``track_counts``.
+        With ``zone_rows`` the zone occupancy comes last on the same stream, into
+        ``zone_buffers(B)`` or ``zone_out`` ([B, 4 + R C] int32 rows, [B, 4 + 2 R C] with
+        ``zone_conf``, which reads ``conf`` too); ``last_zones`` is the buffer written."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -189,6 +242,22 @@ class DevicePostprocess:
                                       K=self.region_cap, q=self.track_q, conf=self.region_conf)
                 words = wide
             self.last_regions = words
+        if self.zone_rows:
+            zws, words = self.zone_buffers(B, crop_w, crop_h)
+            if zone_out is not None:
+                words = zone_out
+            if self.zone_conf and conf is None:
+                raise ValueError("DevicePostprocess.run: zone_conf needs the conf plane")
+            plane = None
+            if self.zone_rows > 1:
+                plane = self._zone_plane.get((crop_w, crop_h))
+                if plane is None:
+                    raise ValueError(f"DevicePostprocess.run: no zone plane set for the {crop_w} x "
+                                     f"{crop_h} crop (set_zone_plane)")
+            hip_ops.zone_stats(labels, words, zws, B=B, H=self.H, W=self.W, crop_h=crop_h,
+                               crop_w=crop_w, R=self.zone_rows, C=self.zone_classes, plane=plane,
+                               conf=conf if self.zone_conf else None)
+            self.last_zones = words
         return rec
 
     def fetch(self, rec: torch.Tensor, frame_ids: Sequence[int], ts: Sequence[float],
@@ -214,3 +283,4 @@ class DevicePostprocess:
         return h.numpy().view(np.uint32).copy()
 
     fetch_regions = fetch_masks  # the same: a uint32 row per frame with a 4-word header
+    fetch_zones = fetch_masks

@@ -3,7 +3,9 @@ and the static outputs they write (``labels``; ``post``: packed records or None;
 --serve_masks run words or None; ``regions``: --serve_regions region words or None (two words a
 record wider with --track_regions, whose per-stream state lives in the engine's one
 DevicePostprocess: the post-processing graphs of all slots advance it in replay order); ``conf``: the
---serve_confidence plane of ``labels``, which the post-processing graph reads, or None).
+--serve_confidence plane of ``labels``, which the post-processing graph reads, or None;
+``zones``: --serve_zones zone words, written by the last kernels of the post-processing chain, or
+None).
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
 may be refilled (None: the model ran on the caller's stream).
 
@@ -53,6 +55,7 @@ class WholeStep:
         self.bgr = bgr = eng.bgr_buffer(frames)
         self.graph, (self.labels, self.post, self.mask, self.regions, self.conf) = _graph(
             lambda: eng._step_all(frames, bgr))
+        self.zones = eng._step_zones  # --serve_zones: the zone words the graph writes, or None
 
     def replay(self) -> None:
         self.graph.replay()
@@ -89,6 +92,7 @@ class SplitStep:
         else:
             self.model, _ = _graph(infer)
         self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab, conf=cf))
+        self.zones = eng.device_zones()  # --serve_zones: the last kernels of the chain, or None
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
     def replay(self) -> None:
@@ -151,13 +155,19 @@ class PartsStep:
         self.regions = reg = torch.zeros((B, 4 + eng.region_words * eng.region_cap), dtype=torch.int32,
                                          device=dev) if eng.region_cap else None
         self.conf = cf = torch.empty_like(lab) if eng.serve_confidence else None
+        self.zones = zn = None
+        if eng.zone_rows:
+            from ..postprocess import zones as ZN
+            self.zones = zn = torch.zeros((B, ZN.frame_words(eng.zone_rows, eng.zone_classes, eng.zone_conf)),
+                                          dtype=torch.int32, device=dev)
         parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
                                                 eng.lut_x, eng.lut_y, out=lab[sl], part=i,
                                                 conf_out=cf[sl] if cf is not None else None),
                   lambda sl=sl: eng._device_post(lab[sl], out=post[sl],
                                                  mask_out=mask[sl] if mask is not None else None,
                                                  region_out=reg[sl] if reg is not None else None,
-                                                 conf=cf[sl] if cf is not None else None))
+                                                 conf=cf[sl] if cf is not None else None,
+                                                 zone_out=zn[sl] if zn is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)
         for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
             run()

@@ -142,10 +142,27 @@ class Engine:
         # (reference_ops.upsample_confidence) and a region has a 7th word, sum_conf.
         # conf_plane: the plane of the last run_device / step (a static buffer, like labels)
         self.serve_confidence = bool(getattr(cfg, "serve_confidence", False))
-        if self.serve_confidence and not cfg.serve_regions:
-            raise ValueError("--serve_confidence requires --serve_regions")
+        serve_zones = bool(getattr(cfg, "serve_zones", False))
+        if self.serve_confidence and not (cfg.serve_regions or serve_zones):
+            raise ValueError("--serve_confidence requires --serve_regions or --serve_zones")
         self.region_words = 7 if self.serve_confidence else 6
         self.conf_plane: Optional[torch.Tensor] = None
+        # --serve_zones: class x zone pixel counts of every label map (postprocess/zones.py).
+        # zone_rows: R = 1 + the zones of --zones (0 = off: no kernel, no buffer); the zones are
+        # loaded and checked here, rasterised per camera geometry in set_camera. zone_packed /
+        # zones: as mask_packed / masks, [B, 4 + R C] words ([B, 4 + 2 R C] with confidence)
+        self.zone_rows, self.zone_classes, self.zone_list, self.zone_plane = 0, 0, [], None
+        if getattr(cfg, "zones", None) and not serve_zones:
+            raise ValueError(f"--zones {cfg.zones} requires --serve_zones")
+        if serve_zones:
+            from ..postprocess import zones as ZN
+            self.zone_list = ZN.load(cfg.zones) if cfg.zones else []
+            self.zone_rows, self.zone_classes = 1 + len(self.zone_list), int(cfg.num_classes)
+            ZN.check_geometry(self.W, self.H, len(self.zone_list), self.zone_classes)  # every crop is within
+        self.zone_conf = bool(self.zone_rows) and self.serve_confidence
+        self.zone_packed: Optional[torch.Tensor] = None
+        self.zones: Optional[np.ndarray] = None
+        self._step_zones = None  # the zone words of the step _step_all issued last
         # --track_regions: every stored region record ends in track_id and age
         # (postprocess/tracks.py), so region_words is two more. On the device the state of the
         # track_streams streams lives in the one DevicePostprocess, and a batch of B frames is
@@ -214,6 +231,11 @@ class Engine:
         self.lut_y = torch.tensor(ly, device=self.device, dtype=torch.int32)
         self._static_step = None  # captured for the previous camera's letterbox,
         self._bound_graphs = {}  # like the bound buffers' steps
+        if self.zone_rows > 1:  # the zones of this camera's crop, in exact integers on the host
+            from ..postprocess import zones as ZN
+            self.zone_plane = ZN.rasterize(self.zone_list, cw, ch)
+            if self._hip_post is not None:
+                self._hip_post.set_zone_plane(self.zone_plane)
 
     # -------------------------------------------------------------- inference
     def to_bgr(self, frames: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -277,17 +299,20 @@ class Engine:
     def _device_post(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                      mask_out: Optional[torch.Tensor] = None,
                      region_out: Optional[torch.Tensor] = None,
-                     conf: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._post_and_mask(labels, out, mask_out, region_out, conf)[0]  # the records alone
+                     conf: Optional[torch.Tensor] = None,
+                     zone_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._post_and_mask(labels, out, mask_out, region_out, conf, zone_out)[0]  # the records alone
 
     def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                        mask_out: Optional[torch.Tensor] = None,
                        region_out: Optional[torch.Tensor] = None,
-                       conf: Optional[torch.Tensor] = None):
+                       conf: Optional[torch.Tensor] = None,
+                       zone_out: Optional[torch.Tensor] = None):
         """(device records of ``labels``, with ``mask_cap`` their run-length masks else None,
         with ``region_cap`` their class regions else None), each right after the other on the
         same stream: one captured graph, a chain, holds all. ``conf``: the confidence plane of
-        ``labels`` (``serve_confidence``), summed per region."""
+        ``labels`` (``serve_confidence``), summed per region. With ``zone_rows`` the zone
+        occupancy ends the chain; its words are ``device_zones()``."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -299,11 +324,20 @@ class Engine:
                                                region_classes=self.region_mask,
                                                region_min_pixels=self.region_min_pixels,
                                                region_conf=self.serve_confidence,
-                                               track_streams=self.track_streams, track_q=self.track_q)
+                                               track_streams=self.track_streams, track_q=self.track_q,
+                                               zone_rows=self.zone_rows, zone_classes=self.zone_classes,
+                                               zone_conf=self.zone_conf)
+            if self.zone_rows > 1:
+                self._hip_post.set_zone_plane(self.zone_plane)
+        kw = {"zone_out": zone_out} if self.zone_rows else {}
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
-                                 mask_out=mask_out, region_out=region_out, conf=conf)
+                                 mask_out=mask_out, region_out=region_out, conf=conf, **kw)
         return (rec, self._hip_post.last_mask if self.mask_cap else None,
                 self._hip_post.last_regions if self.region_cap else None)
+
+    def device_zones(self) -> Optional[torch.Tensor]:
+        """The zone words the device post-processing wrote last (None without ``zone_rows``)."""
+        return self._hip_post.last_zones if self.zone_rows and self._hip_post is not None else None
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
@@ -373,6 +407,25 @@ class Engine:
                       self.region_cap, out=out[b], conf=None if conf is None else conf[b], **kw[b])
         return out
 
+    def host_zones(self, labels, conf=None) -> np.ndarray:
+        """uint32 [B, 4 + R C] zone words of host label maps by the numpy definition
+        (postprocess/zones.py): the CPU path, and a GPU without device post-processing. With
+        ``serve_confidence``, ``conf`` is their confidence plane and the rows are [B, 4 + 2 R C]."""
+        from ..postprocess import zones as ZN
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        if self.zone_conf:
+            if conf is None:
+                raise ValueError("host_zones: serve_confidence needs the conf plane")
+            conf = conf.cpu().numpy() if isinstance(conf, torch.Tensor) else np.asarray(conf)
+        else:
+            conf = None
+        out = np.zeros((lab.shape[0], ZN.frame_words(self.zone_rows, self.zone_classes, self.zone_conf)),
+                       np.uint32)
+        for b in range(lab.shape[0]):
+            ZN.encode(lab[b], self.zone_plane, self.crop_w, self.crop_h, self.zone_classes,
+                      conf=None if conf is None else conf[b], out=out[b], rows=self.zone_rows)
+        return out
+
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
         """One eager step: (labels, packed records or None, mask run words or None, region
         words or None)."""
@@ -382,18 +435,23 @@ class Engine:
         """``_step_outputs`` and, fifth, the confidence plane (None without ``serve_confidence``)."""
         labels, conf = self._infer(frames, bgr)
         if self._use_device_post():
-            return (labels, *self._post_and_mask(labels, conf=conf), conf)
+            out = (labels, *self._post_and_mask(labels, conf=conf), conf)
+            self._step_zones = self.device_zones()
+            return out
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
         host = not self.is_cuda
         mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
         regions = torch.from_numpy(self.host_regions(labels, conf).view(np.int32)) \
             if host and self.region_cap else None
+        self._step_zones = torch.from_numpy(self.host_zones(labels, conf).view(np.int32)) \
+            if host and self.zone_rows else None
         post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
         return labels, post, mask, regions, conf
 
     def _step_device(self, frames: torch.Tensor):
         labels, post, self.mask_packed, self.region_packed, self.conf_plane = self._step_all(frames)
+        self.zone_packed = self._step_zones
         return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
@@ -529,6 +587,7 @@ class Engine:
         # written by the replay, like the records; and when the frame buffer may be refilled
         self.mask_packed, self.region_packed, self.last_consumed = step.mask, step.regions, step.consumed
         self.conf_plane = step.conf
+        self.zone_packed = step.zones
         return step.labels, step.post
 
     # ------------------------------------------------------------ post/host
@@ -585,6 +644,8 @@ class Engine:
                 self.masks = self.host_masks(labels)
             if self.region_cap:
                 self.regions = self.host_regions(labels, self.conf_plane, streams)
+            if self.zone_rows:
+                self.zones = self.host_zones(labels, self.conf_plane)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         if self._use_device_post():
@@ -603,6 +664,8 @@ class Engine:
                     self.masks = self._hip_post.fetch_masks(self.mask_packed)
                 if self.region_cap:
                     self.regions = self._hip_post.fetch_regions(self.region_packed)
+                if self.zone_rows:
+                    self.zones = self._hip_post.fetch_zones(self.zone_packed)
             else:
                 recs = None
         self.stream.synchronize()
@@ -610,6 +673,8 @@ class Engine:
             self.masks = self.host_masks(labels)
         if self.region_cap and post is None:
             self.regions = self.host_regions(labels, self.conf_plane, streams)
+        if self.zone_rows and post is None:
+            self.zones = self.host_zones(labels, self.conf_plane)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

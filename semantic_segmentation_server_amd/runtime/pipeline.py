@@ -154,6 +154,10 @@ class Producer(threading.Thread):
                         if getattr(self.engine, "track_regions", False):
                             kw["tracks"] = True
                         self.hub.push_regions(regions, np.array([ids, streams, ts], np.float64).T, **kw)
+                    zones = getattr(self.engine, "zones", None)
+                    if zones is not None and hasattr(self.hub, "push_zones"):  # --serve_zones
+                        self.hub.push_zones(zones, np.array([ids, streams, ts], np.float64).T,
+                                            conf=bool(getattr(self.engine, "zone_conf", False)))
                 self.metrics.observe("objects_per_frame", len(recs) / max(1, len(ids)))
                 self.metrics.observe("buffer_depth", self.hub.depth)
                 dt = (time.perf_counter() - t0) * 1e3

@@ -146,6 +146,14 @@ class StoredRegions(NamedTuple):
     tracks: bool = False  # the records end in track_id and age (--track_regions)
 
 
+class StoredZones(NamedTuple):
+    """A stream's latest zone occupancy: the words are the hub's own copy."""
+    frame_id: int
+    ts: float
+    words: np.ndarray  # uint32[4 + R C] (postprocess/zones.py); uint32[4 + 2 R C] with conf
+    conf: bool = False  # the words end in the sum_conf block (--serve_confidence)
+
+
 def latest_rows(rows: np.ndarray, meta: np.ndarray, unit: int = 1):
     """Of a collected batch of uint32 rows with a 4-word header whose word 0 counts the
     payload entries (``unit`` words each; run words: 1, region words: 6, or 7 with
@@ -175,6 +183,7 @@ class ResultHub:
         self._lock = threading.Lock()
         self._masks: Dict[int, StoredMask] = {}
         self._regions: Dict[int, StoredRegions] = {}
+        self._zones: Dict[int, StoredZones] = {}
 
     def get(self, stream: int) -> Optional[ResultBuffer]:
         """The stream's buffer, or None for a stream id the hub does not serve (RPC
@@ -252,6 +261,33 @@ class ResultHub:
         """The stream's latest regions (frame_id, ts, words), or None before the first ones."""
         with self._lock:
             return self._regions.get(int(stream))
+
+    # ---- zone occupancy (--serve_zones): the LATEST zone words per stream
+    def put_zones(self, stream: int, frame_id: int, ts: float, words: np.ndarray,
+                  conf: bool = False) -> None:
+        """Store a COPY of ``words`` (header + [R][C] blocks, postprocess/zones.py) as the
+        stream's latest zone occupancy. ``conf``: the ``sum_conf`` block follows ``pixels``."""
+        z = StoredZones(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True), bool(conf))
+        with self._lock:
+            self._zones[int(stream)] = z
+
+    def push_zones(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False) -> None:
+        """As ``push_masks`` for [F, 4 + R C] zone words ([F, 4 + 2 R C] with ``conf``): of
+        several frames of one stream only the last is copied, whole (every word is used)."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint32:
+            rows = rows.view(np.uint32)
+        last: Dict[int, int] = {}
+        for i in range(len(rows)):
+            last[int(meta[i, 1])] = i
+        for st, i in last.items():
+            self.put_zones(st, int(meta[i, 0]), float(meta[i, 2]), rows[i], conf)
+
+    def zones(self, stream: int) -> Optional["StoredZones"]:
+        """The stream's latest zone occupancy (frame_id, ts, words, conf), or None before the
+        first one."""
+        with self._lock:
+            return self._zones.get(int(stream))
 
     @property
     def depth(self) -> int:

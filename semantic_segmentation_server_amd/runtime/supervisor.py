@@ -282,10 +282,11 @@ class _RingHub:
     the latest masks / regions to the incarnation's channels)."""
 
     def __init__(self, ring: _RecordRing, masks: Optional[_WordChannel] = None,
-                 regions: Optional[_WordChannel] = None):
+                 regions: Optional[_WordChannel] = None, zones: Optional[_WordChannel] = None):
         self.ring = ring
         self.masks = masks
         self.region_ch = regions
+        self.zone_ch = zones
         self.buffers = {}
         self.depth = 0
 
@@ -309,6 +310,14 @@ class _RingHub:
         for st, fid, ts, words in latest_rows(rows, meta, self.region_ch.unit):
             self.region_ch.write(st, fid, ts, words)
 
+    def push_zones(self, rows: np.ndarray, meta: np.ndarray, conf: bool = False) -> None:
+        """As ResultHub.push_zones. A frame's zone words are R entries (word 0) of the channel's
+        unit, C words (2 C with confidence: from the one config, like the zone names)."""
+        if self.zone_ch is None:
+            return
+        for st, fid, ts, words in latest_rows(rows, meta, self.zone_ch.unit):
+            self.zone_ch.write(st, fid, ts, words)
+
 
 def _fault_for(spec: Optional[str], rank: int, incarnation: int):
     """(kind, step) of the fault injected into this worker incarnation, or None."""
@@ -324,7 +333,7 @@ def _fault_for(spec: Optional[str], rank: int, incarnation: int):
 
 def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnation: int,
                  max_steps: Optional[int], mask_name: Optional[str] = None,
-                 region_name: Optional[str] = None) -> None:
+                 region_name: Optional[str] = None, zone_name: Optional[str] = None) -> None:
     """Child process: rank ``rank``'s producer, reporting through the ring and ``q``."""
     logging.basicConfig(level=getattr(logging, cfg.log_level.upper(), logging.INFO),
                         format=f"%(asctime)s %(levelname)s worker{rank}: %(message)s")
@@ -339,6 +348,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     ring = _RecordRing(name=ring_name)
     masks = _WordChannel(name=mask_name) if mask_name else None
     regions = _WordChannel(name=region_name) if region_name else None
+    zones = _WordChannel(name=zone_name) if zone_name else None
     metrics = Metrics()
     device = None
     if cfg.device != "cpu" and torch.cuda.is_available() and torch.cuda.device_count() > rank:
@@ -349,7 +359,8 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
                            cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank,
                            pixel_format=cfg.pixel_format)
                for s in range(S)]
-    prod = Producer(engine, sources, _RingHub(ring, masks, regions), metrics, cfg.batch, max_steps=max_steps)
+    prod = Producer(engine, sources, _RingHub(ring, masks, regions, zones), metrics, cfg.batch,
+                    max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
 
     def on_step(n: int) -> None:  # step progress, published by the producer thread itself
@@ -400,6 +411,7 @@ class _Worker:
         self.ring: Optional[_RecordRing] = None
         self.masks: Optional[_WordChannel] = None
         self.regions: Optional[_WordChannel] = None
+        self.zones: Optional[_WordChannel] = None
         self.q = None
         self.up = False
         self.started = 0.0
@@ -440,6 +452,14 @@ class SupervisedServer:
                                            pixel_format=cfg.pixel_format)
         self.grpc_server, self.port = S.make_server(cfg.max_workers, cfg.port, cfg.host)
         labels = load_labels(cfg.labels)
+        # --serve_zones: the zone file is read here too (its errors stop the server before any
+        # worker starts); the names stay on this side, the workers send integer words alone
+        self.zone_names = None
+        if getattr(cfg, "serve_zones", False):
+            from ..postprocess import zones as ZN
+            zl = ZN.load(cfg.zones) if cfg.zones else []
+            ZN.check_geometry(cfg.input_size, cfg.input_size, len(zl), cfg.num_classes)
+            self.zone_names = ZN.names(zl)
         S.add_v1_servicer(S.SemanticSegmentationServicer(self.hub, labels, cfg.num_detections,
                                                          self.camera_res, metrics=self.metrics),
                           self.grpc_server)
@@ -449,7 +469,8 @@ class SupervisedServer:
                                                            streams, self.metrics, self._health,
                                                            serve_masks=cfg.serve_masks,
                                                            serve_regions=cfg.serve_regions,
-                                                           model_size=(cfg.input_size, cfg.input_size)),
+                                                           model_size=(cfg.input_size, cfg.input_size),
+                                                           zone_names=self.zone_names),
                           self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
         self._ctx = mp.get_context("spawn")
@@ -496,10 +517,15 @@ class SupervisedServer:
                                  unit=(7 if self.cfg.serve_confidence else 6)
                                  + (2 if getattr(self.cfg, "track_regions", False) else 0)) \
             if self.cfg.serve_regions else None
+        # zone words: R entries of C words each (2 C with confidence)
+        w.zones = _WordChannel(self.S, len(self.zone_names), w.rank * self.S,
+                               unit=int(self.cfg.num_classes) * (2 if self.cfg.serve_confidence else 1)) \
+            if self.zone_names else None
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
                                          self.max_steps, w.masks.name if w.masks is not None else None,
-                                         w.regions.name if w.regions is not None else None),
+                                         w.regions.name if w.regions is not None else None,
+                                         w.zones.name if w.zones is not None else None),
                                    daemon=True)
         w.proc.start()
         w.started = time.time()
@@ -539,6 +565,9 @@ class SupervisedServer:
                 # unit 6, 7 (confidence), 8 (tracks) or 9 (both)
                 self.hub.put_regions(stream, fid, ts, words, conf=w.regions.unit in (7, 9),
                                      tracks=w.regions.unit in (8, 9))
+        if w.zones is not None:
+            for stream, fid, ts, words in w.zones.pull():
+                self.hub.put_zones(stream, fid, ts, words, conf=bool(self.cfg.serve_confidence))
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
@@ -618,6 +647,9 @@ class SupervisedServer:
         if w.regions is not None:
             w.regions.close()
             w.regions = None
+        if w.zones is not None:
+            w.zones.close()
+            w.zones = None
         if w.q is not None:
             try:
                 w.q.close()

@@ -64,10 +64,18 @@ class Server:
                                                    streams, self.metrics, self._health,
                                                    serve_masks=cfg.serve_masks,
                                                    serve_regions=cfg.serve_regions,
-                                                   model_size=(cfg.input_size, cfg.input_size))
+                                                   model_size=(cfg.input_size, cfg.input_size),
+                                                   zone_names=self._zone_names())
         S.add_v1_servicer(self.v1, self.grpc_server)
         S.add_v2_servicer(self.v2, self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
+
+    def _zone_names(self):
+        """--serve_zones: the names of the zone rows ("frame" first), from the engine's zones."""
+        if not getattr(self.engine, "zone_rows", 0):
+            return None
+        from .postprocess import zones as ZN
+        return ZN.names(self.engine.zone_list)
 
     def _health(self):
         alive = self.producer.is_alive() and (time.time() - self.producer.alive_ts) < 30
