@@ -516,6 +516,31 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("out"), py::arg("ws"), py::arg("stream"));
   m.attr("ZONE_STATS_CHUNK") = zone_stats_chunk();
 
+  m.def("zone_presence_workspace_bytes", &zone_presence_workspace_bytes, py::arg("B"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("tracks"));
+  m.def("zone_presence_state_bytes", &zone_presence_state_bytes, py::arg("streams"), py::arg("K"),
+        py::arg("R"));
+  m.def("zone_presence",
+        [](uintptr_t rows, uintptr_t cr_ws, uintptr_t tws, uintptr_t plane, int B, int crop_h, int crop_w,
+           int K, int R, int record_words, uintptr_t out, uintptr_t ws, uintptr_t state, uintptr_t pred,
+           uintptr_t last, int streams, int q, uintptr_t stream) {
+          ZonePresenceParams p;
+          p.rows = P<const uint32_t>(rows); p.cr_ws = P<const uint32_t>(cr_ws);
+          p.tws = P<const uint32_t>(tws); p.plane = P<const uint32_t>(plane);
+          p.B = B; p.crop_h = crop_h; p.crop_w = crop_w; p.K = K; p.R = R; p.record_words = record_words;
+          p.out = P<uint32_t>(out); p.ws = P<uint32_t>(ws); p.state = P<uint32_t>(state);
+          p.pred = P<const int>(pred); p.last = P<const int>(last); p.streams = streams; p.q = q;
+          zone_presence(p, S(stream));
+        },
+        py::arg("rows"), py::arg("cr_ws"), py::arg("tws"), py::arg("plane"), py::arg("B"),
+        py::arg("crop_h"), py::arg("crop_w"), py::arg("K"), py::arg("R"), py::arg("record_words"),
+        py::arg("out"), py::arg("ws"), py::arg("state"), py::arg("pred"), py::arg("last"),
+        py::arg("streams"), py::arg("q"), py::arg("stream"));
+  m.def("zone_presence_copy_used", [](uintptr_t src, uintptr_t dst, int B, int K, int U, uintptr_t stream) {
+    zone_presence_copy_used(P<const uint32_t>(src), P<uint32_t>(dst), B, K, U, S(stream));
+  });
+  m.attr("ZONE_PRESENCE_CHUNK") = zone_presence_chunk();
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

@@ -560,6 +560,18 @@ __device__ __forceinline__ uint32_t tr_stored(const TrArgs& t, int b) {  // min(
   return n < (uint32_t)t.K ? n : (uint32_t)t.K;
 }
 
+// The rank of pixel i's stored region from a frame's class-region workspace after its run
+// (parent[N], cnt[N]), kNoSlot without one.
+__device__ __forceinline__ uint16_t resolve_slot(const uint32_t* parent, int N, int i) {
+  const uint32_t* cnt = parent + N;
+  uint32_t slot = kNoSlot;
+  if (parent[i] != kNone) {
+    const uint32_t c = cnt[find_plain(parent, (uint32_t)i)];
+    if (c & kSlotBit) slot = c & ~kSlotBit;
+  }
+  return (uint16_t)slot;
+}
+
 __global__ __launch_bounds__(kThreads) void k_tr_slots(TrArgs t) {
   const int b = blockIdx.y;
   const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -567,14 +579,17 @@ __global__ __launch_bounds__(kThreads) void k_tr_slots(TrArgs t) {
   const uint32_t used = tr_stored(t, b) * (uint32_t)t.K;
   for (uint32_t j = (uint32_t)i; j < used; j += gridDim.x * kThreads) tab[j] = 0;
   if (i >= t.N) return;
-  const uint32_t* parent = t.ws + (size_t)b * frame_words((size_t)t.N);
-  const uint32_t* cnt = parent + t.N;
-  uint32_t slot = kNoSlot;
-  if (parent[i] != kNone) {
-    const uint32_t c = cnt[find_plain(parent, (uint32_t)i)];
-    if (c & kSlotBit) slot = c & ~kSlotBit;
-  }
-  tr_plane(t, b)[i] = (uint16_t)slot;
+  tr_plane(t, b)[i] = resolve_slot(t.ws + (size_t)b * frame_words((size_t)t.N), t.N, i);
+}
+
+// The slot plane alone, for a consumer without tracking (zone_presence.hip): planes[b] is a
+// plane of plane_words(N) words, as tr_plane's.
+__global__ __launch_bounds__(kThreads) void k_cr_slot_plane(const uint32_t* ws, uint32_t* planes, int N) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= N) return;
+  reinterpret_cast<uint16_t*>(planes + (size_t)b * plane_words((size_t)N))[i] =
+      resolve_slot(ws + (size_t)b * frame_words((size_t)N), N, i);
 }
 
 __global__ __launch_bounds__(kThreads) void k_tr_overlap(TrArgs t) {
@@ -830,6 +845,22 @@ void class_regions(const ClassRegionsParams& p, hipStream_t s) {
 size_t region_tracks_workspace_bytes(int B, int crop_h, int crop_w, int K) {
   const size_t N = (size_t)crop_h * (size_t)crop_w;
   return ((size_t)B * plane_words(N) + (size_t)B * K * K + (size_t)B * K) * sizeof(uint32_t);
+}
+
+// the layout of the tracking workspace, for zone_presence.hip
+size_t region_slot_plane_words(int crop_h, int crop_w) { return plane_words((size_t)crop_h * (size_t)crop_w); }
+size_t region_tracks_planes_offset_words() { return 0; }
+size_t region_tracks_links_offset_words(int B, int crop_h, int crop_w, int K) {
+  return (size_t)B * plane_words((size_t)crop_h * (size_t)crop_w) + (size_t)B * K * K;
+}
+
+void class_regions_slot_planes(const uint32_t* ws, uint32_t* planes, int B, int crop_h, int crop_w,
+                               hipStream_t s) {
+  const long long N = (long long)crop_h * crop_w;
+  if (B <= 0 || B > 65535 || crop_h <= 0 || crop_w <= 0 || N >= (1LL << 24) || !ws || !planes)
+    check(hipErrorInvalidValue, "class_regions_slot_planes: bad arguments");
+  hipLaunchKernelGGL(k_cr_slot_plane, dim3(cdiv(N, kThreads), B), dim3(kThreads), 0, s, ws, planes, (int)N);
+  check_launch("class_regions_slot_planes");
 }
 
 size_t region_tracks_state_bytes(int streams, int crop_h, int crop_w) {

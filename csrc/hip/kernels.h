@@ -422,4 +422,47 @@ size_t zone_stats_workspace_bytes(int B, int R, int C, bool conf);
 int zone_stats_chunk();  // flat pixels per workgroup
 void zone_stats(const ZoneStatsParams& p, hipStream_t s);
 
+// ---- the slot planes and the tracking workspace's layout (class_regions.hip) ------------------
+// A slot plane is uint16[N] in region_slot_plane_words(crop_h, crop_w) words: per flat crop pixel
+// the rank of its stored region, 0xFFFF without one. class_regions_slot_planes resolves the
+// planes of B frames from the class_regions workspace `ws` after its run (what k_tr_slots does
+// for region_tracks, which keeps its own: B planes at region_tracks_planes_offset_words() of its
+// workspace, and link[b][a] -- the predecessor of a matched region, 0xFFFFFFFF otherwise -- as
+// [B][K] words at region_tracks_links_offset_words(B, crop_h, crop_w, K)).
+size_t region_slot_plane_words(int crop_h, int crop_w);
+size_t region_tracks_planes_offset_words();
+size_t region_tracks_links_offset_words(int B, int crop_h, int crop_w, int K);
+void class_regions_slot_planes(const uint32_t* ws, uint32_t* planes, int B, int crop_h, int crop_w,
+                               hipStream_t s);
+
+// ---- zone presence (zone_presence.hip; the definition is postprocess/presence.py) ------------
+// After class_regions (and region_tracks, when `tws` is set) on the same stream, with their B,
+// crop and K: out[b] = uint32[4 + U K], U = 2 + R (2 + 2 R with tracking) = n, N, crop_w, crop_h,
+// then per stored region a < n = min(n_regions, K): (label << 24) | root, track_id, P[a][0 .. R),
+// the pixels of the region in each zone row, and with tracking D[a][0 .. R), the dwell of its track
+// in each row. `rows`: the region rows as served ([B, 4 + record_words K]; record_words 6 | 7,
+// with tracking the rows with tracks: 8 | 9). Every word of out is written by every run.
+struct ZonePresenceParams {
+  const uint32_t* rows = nullptr;
+  const uint32_t* cr_ws = nullptr;   // class_regions' workspace after its run (read without tracking)
+  const uint32_t* tws = nullptr;     // region_tracks' workspace after its run, or null: no tracking
+  const uint32_t* plane = nullptr;   // [crop_h, crop_w], or null when R == 1; shared by all frames
+  int B = 0, crop_h = 0, crop_w = 0, K = 0, R = 0, record_words = 6;
+  uint32_t* out = nullptr;           // [B, 4 + U K]
+  uint32_t* ws = nullptr;            // zone_presence_workspace_bytes(B, crop_h, crop_w, tracking)
+  // tracking only: the carried dwell state (zone_presence_state_bytes; all zero: a reset), the
+  // batch layout of region_tracks, q = max(1, round(1024 * min share)), 1 .. 1024
+  uint32_t* state = nullptr;
+  const int* pred = nullptr;
+  const int* last = nullptr;
+  int streams = 0, q = 512;
+};
+size_t zone_presence_workspace_bytes(int B, int crop_h, int crop_w, bool tracks);
+size_t zone_presence_state_bytes(int streams, int K, int R);
+int zone_presence_chunk();  // flat pixels per workgroup
+void zone_presence(const ZonePresenceParams& p, hipStream_t s);
+// src [B, 4 + U K] (zone_presence's out) -> dst, the same layout in pinned host memory: per frame
+// only the 4 + U n used words are written, by a kernel on stream s.
+void zone_presence_copy_used(const uint32_t* src, uint32_t* dst, int B, int K, int U, hipStream_t s);
+
 }  // namespace ssa

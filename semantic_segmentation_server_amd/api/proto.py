@@ -218,6 +218,43 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "zones", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "Zone")
     _field(m, "has_confidence", 9, F.TYPE_BOOL)  # the classes carry a confidence
 
+    m = fd.message_type.add(); m.name = "PresenceRequest"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+
+    # one user zone a region has pixels in (postprocess/presence.py); share and inside are
+    # computed from the stored integer counts
+    m = fd.message_type.add(); m.name = "ZoneHit"
+    _field(m, "index", 1, F.TYPE_INT32)
+    _field(m, "name", 2, F.TYPE_STRING)
+    _field(m, "pixels", 3, F.TYPE_UINT32)
+    _field(m, "share", 4, F.TYPE_FLOAT)    # pixels / region pixels
+    _field(m, "inside", 5, F.TYPE_BOOL)
+    _field(m, "dwell", 6, F.TYPE_UINT32)   # 0 without has_tracks
+
+    m = fd.message_type.add(); m.name = "RegionPresence"
+    _field(m, "index", 1, F.TYPE_INT32)
+    _field(m, "label", 2, F.TYPE_STRING)
+    _field(m, "class_id", 3, F.TYPE_INT32)
+    _field(m, "root", 4, F.TYPE_UINT32)
+    _field(m, "pixels", 5, F.TYPE_UINT32)
+    _field(m, "track_id", 6, F.TYPE_UINT32)
+    _field(m, "age", 7, F.TYPE_UINT32)
+    # the user zones with pixels > 0, index ascending
+    _field(m, "zones", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "ZoneHit")
+
+    # the region x zone pixel overlap of the stream's latest frame
+    m = fd.message_type.add(); m.name = "ZonePresence"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "frame_id", 2, F.TYPE_INT64)
+    _field(m, "timestamp", 3, F.TYPE_DOUBLE)
+    _field(m, "width", 4, F.TYPE_INT32)    # crop region, model-resolution pixels
+    _field(m, "height", 5, F.TYPE_INT32)
+    _field(m, "model_width", 6, F.TYPE_INT32)
+    _field(m, "model_height", 7, F.TYPE_INT32)
+    _field(m, "regions", 8, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "RegionPresence")
+    _field(m, "has_tracks", 9, F.TYPE_BOOL)   # the regions carry track_id, age and dwell
+    _field(m, "min_share", 10, F.TYPE_FLOAT)  # q / 1024 of --presence_min_share
+
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"
     E = ".sem_seg_server.Empty"
@@ -228,6 +265,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _method(svc, "GetSegmentationMask", P + "MaskRequest", P + "SegmentationMask")
     _method(svc, "GetClassRegions", P + "RegionRequest", P + "ClassRegions")
     _method(svc, "GetZoneOccupancy", P + "ZoneRequest", P + "ZoneOccupancy")
+    _method(svc, "GetZonePresence", P + "PresenceRequest", P + "ZonePresence")
     return fd
 
 
@@ -291,6 +329,10 @@ ZoneRequest = _cls("sem_seg_server.v2.ZoneRequest")
 ZoneClass = _cls("sem_seg_server.v2.ZoneClass")
 Zone = _cls("sem_seg_server.v2.Zone")
 ZoneOccupancy = _cls("sem_seg_server.v2.ZoneOccupancy")
+PresenceRequest = _cls("sem_seg_server.v2.PresenceRequest")
+ZoneHit = _cls("sem_seg_server.v2.ZoneHit")
+RegionPresence = _cls("sem_seg_server.v2.RegionPresence")
+ZonePresence = _cls("sem_seg_server.v2.ZonePresence")
 
 # ---- grpc.health.v1 ---------------------------------------------------------
 HealthCheckRequest = _cls("grpc.health.v1.HealthCheckRequest")
@@ -308,6 +350,7 @@ V2_METHODS = {
     "GetSegmentationMask": (MaskRequest, SegmentationMask),
     "GetClassRegions": (RegionRequest, ClassRegions),
     "GetZoneOccupancy": (ZoneRequest, ZoneOccupancy),
+    "GetZonePresence": (PresenceRequest, ZonePresence),
 }
 
 

@@ -74,8 +74,12 @@ class SemanticSegmentationV2Servicer:
                  streams: Optional[list] = None, metrics=None,
                  health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None, *,
                  serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0),
-                 serve_regions: bool = False, zone_names: Optional[list] = None):
+                 serve_regions: bool = False, zone_names: Optional[list] = None,
+                 presence_q: int = 0):
         self.hub = hub
+        # --serve_presence: q of --presence_min_share (0: GetZonePresence is off); the rows are
+        # those of zone_names, and every stored item says whether it carries tracks
+        self.presence_q = int(presence_q)
         # --serve_zones: the names of the zone rows, "frame" first (None: GetZoneOccupancy is off)
         self.zone_names = list(zone_names) if zone_names else None
         self.serve_regions = bool(serve_regions)  # --serve_regions: GetClassRegions is enabled
@@ -207,6 +211,44 @@ class SemanticSegmentationV2Servicer:
             stream_id=stream, frame_id=z.frame_id, timestamp=z.ts, width=st.crop_w, height=st.crop_h,
             model_width=int(self.model_size[0]), model_height=int(self.model_size[1]), zones=out,
             has_confidence=has_conf)
+
+    def GetZonePresence(self, request, context):
+        """The pixels of every class region inside every zone of the stream's latest frame. The
+        producer stores integers (postprocess/presence.py); share and inside are computed here
+        from them, for the one stream an RPC asks for."""
+        from ..postprocess import presence as PR
+        stream = int(request.stream_id)
+        if not self.presence_q or self.zone_names is None:
+            context.set_code(grpc.StatusCode.FAILED_PRECONDITION)
+            context.set_details("zone presence is not enabled (start the server with --serve_presence)")
+            return P.ZonePresence()
+        if self.hub.get(stream) is None:
+            context.set_code(grpc.StatusCode.NOT_FOUND)
+            context.set_details(f"unknown stream_id {request.stream_id}")
+            return P.ZonePresence()
+        z = self.hub.presence(stream)
+        if z is None:
+            context.set_code(grpc.StatusCode.UNAVAILABLE)
+            context.set_details(f"no frame of stream {stream} collected yet")
+            return P.ZonePresence()
+        tr = bool(z.tracks)
+        pr = PR.decode(z.words, len(self.zone_names), tracks=tr)
+        ins = PR.inside(pr.P, self.presence_q)
+        out = []
+        for a in range(pr.n):
+            px = int(pr.P[a, 0])
+            hits = [P.ZoneHit(index=r, name=self.zone_names[r], pixels=int(pr.P[a, r]),
+                              share=int(pr.P[a, r]) / px if px else 0.0, inside=bool(ins[a, r]),
+                              dwell=int(pr.D[a, r]) if tr else 0)
+                    for r in range(1, pr.P.shape[1]) if pr.P[a, r] > 0]
+            out.append(P.RegionPresence(index=a, label=label_name(self.labels, int(pr.label[a])),
+                                        class_id=int(pr.label[a]), root=int(pr.root[a]), pixels=px,
+                                        track_id=int(pr.track_id[a]), age=int(pr.D[a, 0]) if tr else 0,
+                                        zones=hits))
+        return P.ZonePresence(
+            stream_id=stream, frame_id=z.frame_id, timestamp=z.ts, width=pr.crop_w, height=pr.crop_h,
+            model_width=int(self.model_size[0]), model_height=int(self.model_size[1]), regions=out,
+            has_tracks=tr, min_share=self.presence_q / PR.Q_ONE)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

@@ -130,6 +130,26 @@ def print_zones(m) -> None:
                   ("  conf {:.3f}".format(c.confidence) if m.has_confidence else ""))
 
 
+def fetch_presence(target: str, stream: int = 0):
+    """The ZonePresence message of the stream's latest frame (v2 GetZonePresence)."""
+    with grpc.insecure_channel(target) as ch:
+        return SemanticSegmentationV2Stub(ch).GetZonePresence(P.PresenceRequest(stream_id=stream))
+
+
+def print_presence(m) -> None:
+    print("stream {} frame {} ts {:.3f}: {} regions in {} x {} (model {} x {}), min share {:.3f}".format(
+        m.stream_id, m.frame_id, m.timestamp, len(m.regions), m.width, m.height, m.model_width,
+        m.model_height, m.min_share))
+    for r in m.regions:
+        print("  region {:>3} {:>3} {:<20} {:>8} px  root {:>8}".format(
+            r.index, r.class_id, r.label, r.pixels, r.root) +
+              ("  track {:>5}  age {:>5}".format(r.track_id, r.age) if m.has_tracks else ""))
+        for h in r.zones:
+            print("    zone {:>2} {:<16} {:>8} px  share {:.4f}  {}".format(
+                h.index, h.name, h.pixels, h.share, "inside " if h.inside else "outside") +
+                  ("  dwell {:>5}".format(h.dwell) if m.has_tracks else ""))
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="sem_seg_server example client")
     p.add_argument("--target", default="localhost:50051")
@@ -148,7 +168,19 @@ def main(argv=None) -> int:
     p.add_argument("--zones_of", nargs="?", type=int, const=0, default=None, metavar="STREAM",
                    help="fetch the zone occupancy of the stream's latest frame (server run with "
                         "--serve_zones) and print, per zone, one line per class present")
+    p.add_argument("--presence", nargs="?", type=int, const=0, default=None, metavar="STREAM",
+                   help="fetch the zone presence of the stream's latest frame (server run with "
+                        "--serve_presence) and print one line per region and zone hit")
     a = p.parse_args(argv)
+    if a.presence is not None:
+        try:
+            m = fetch_presence(a.target, a.presence)
+        except grpc.RpcError as err:
+            print(err.details())
+            print("{}, {}".format(err.code().name, err.code().value))
+            return 1
+        print_presence(m)
+        return 0
     if a.zones_of is not None:
         try:
             m = fetch_zones(a.target, a.zones_of)

@@ -72,6 +72,8 @@ class Config:
     track_min_overlap: float = 0.25        # overlap / smaller region that continues a track, in (0, 1]
     serve_zones: bool = False              # class x zone pixel counts of every label map (v2 GetZoneOccupancy)
     zones: Optional[str] = None            # zone file (JSON, postprocess/zones.py); None: the frame zone alone
+    serve_presence: bool = False           # region x zone pixel overlap, per-track dwell (v2 GetZonePresence)
+    presence_min_share: float = 0.5        # share of a region's pixels inside a zone that puts it inside, in (0, 1]
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -105,6 +107,11 @@ class Config:
                              "class region across frames (v2 GetClassRegions)")
         if self.track_regions and not 0.0 < float(self.track_min_overlap) <= 1.0:
             raise ValueError(f"--track_min_overlap {self.track_min_overlap} outside (0, 1]")
+        if self.serve_presence and not (self.serve_regions and self.serve_zones):
+            raise ValueError("--serve_presence requires --serve_regions and --serve_zones: presence is "
+                             "the overlap of the class regions with the zones (v2 GetZonePresence)")
+        if self.serve_presence and not 0.0 < float(self.presence_min_share) <= 1.0:
+            raise ValueError(f"--presence_min_share {self.presence_min_share} outside (0, 1]")
         if self.pixel_format != "bgr":
             if self.camera_width % 2:
                 raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
@@ -212,6 +219,14 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--zones", default=d.zones, metavar="FILE.json",
                    help="zone file: up to 32 named polygons or rectangles in normalised camera "
                         "coordinates; requires --serve_zones (without it only the frame zone is served)")
+    p.add_argument("--serve_presence", action="store_true",
+                   help="count the pixels of every class region inside every zone on the device and "
+                        "serve them per stream (v2 GetZonePresence); with --track_regions also how "
+                        "many frames each track has been inside each zone; requires --serve_regions "
+                        "and --serve_zones")
+    p.add_argument("--presence_min_share", type=float, default=d.presence_min_share,
+                   help="share of a region's pixels inside a zone from which the region counts as "
+                        "inside it (0 < share <= 1)")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

@@ -1466,6 +1466,105 @@ def zone_stats(labels, out, ws, *, B, H, W, crop_h, crop_w, R, C, plane=None, co
     return out
 
 
+def zone_presence_workspace_bytes(B, crop_h, crop_w, tracks: bool = False) -> int:
+    return int(_hip_mod().zone_presence_workspace_bytes(int(B), int(crop_h), int(crop_w), bool(tracks)))
+
+
+def zone_presence_state_bytes(streams, K, R) -> int:
+    return int(_hip_mod().zone_presence_state_bytes(int(streams), int(K), int(R)))
+
+
+def zone_presence_chunk() -> int:
+    """Flat pixels per workgroup of ``zone_presence`` (the module's ZONE_PRESENCE_CHUNK)."""
+    return int(_hip_mod().ZONE_PRESENCE_CHUNK)
+
+
+def zone_presence(rows, out, ws, cr_ws, *, B, crop_h, crop_w, K, R, plane=None, conf=False,
+                  tws=None, state=None, tables=None, counts=None, q=None):
+    """Zone presence of the class regions that ``class_regions`` (and, with ``tws``,
+    ``region_tracks``) just wrote on the current stream (csrc/hip/zone_presence.hip; the format is
+    postprocess/presence.py's): per frame ``out[b] = [n, N, crop_w, crop_h, entries]``, an entry per
+    stored region: ``(label << 24) | root, track_id, P[R]`` and with tracking ``D[R]``. ``rows``: the
+    region rows as served, [B, 4 + 6 K] (7 with ``conf``), with tracking the rows with tracks
+    ([B, 4 + 8 K], 9); ``cr_ws``: the class-region workspace of that run; ``plane``: the zone plane
+    (uint32/int32 [crop_h, crop_w]; None iff ``R == 1``); ``out``: uint32/int32 [B, 4 + (2 + R) K],
+    with tracking [B, 4 + (2 + 2 R) K]; ``ws``: uint8, at least ``zone_presence_workspace_bytes``.
+    Tracking (all or none of them): ``tws`` the workspace of that ``region_tracks`` run, ``state``
+    the carried dwell state, exactly ``zone_presence_state_bytes(len(counts), K, R)`` bytes (zero:
+    a reset), ``tables`` / ``counts`` as for ``region_tracks``, ``q``: ``presence.quantize(min
+    share)``. Every word of ``out`` is written."""
+    from ..postprocess import presence as PR
+    B, crop_h, crop_w, K, R = (int(v) for v in (B, crop_h, crop_w, K, R))
+    tracking = [v is not None for v in (tws, state, tables, counts, q)]
+    if any(tracking) and not all(tracking):
+        raise ValueError("zone_presence: tws, state, tables, counts and q go together")
+    tracks = all(tracking)
+    if B < 1 or B > 65535:
+        raise ValueError(f"zone_presence: bad batch {B}")
+    if crop_h < 1 or crop_w < 1 or crop_h * crop_w >= PR.MAX_PIXELS:
+        raise ValueError(f"zone_presence: bad crop {crop_h} x {crop_w}")
+    if not 1 <= K <= REGION_MAX_K or PR.MAX_REGIONS != REGION_MAX_K:
+        raise ValueError(f"zone_presence: K {K} outside 1 .. {REGION_MAX_K}")
+    if not 1 <= R <= 1 + PR.MAX_ZONES:
+        raise ValueError(f"zone_presence: R {R} outside 1 .. {1 + PR.MAX_ZONES}")
+    if (plane is None) != (R == 1):
+        raise ValueError(f"zone_presence: R = {R} {'needs a' if R > 1 else 'takes no'} zone plane")
+    rw = (7 if conf else 6) + (2 if tracks else 0)
+    for t, name, width in ((rows, "rows", rw), (out, "out", PR.unit(R, tracks))):
+        if t.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"{name}: expected uint32 or int32, got {t.dtype}")
+        _chk(t, t.dtype, name)
+        if tuple(t.shape) != (B, 4 + width * K):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {4 + width * K})")
+    if rows.data_ptr() == out.data_ptr():
+        raise ValueError("zone_presence: rows and out are the same buffer")
+    if plane is not None:
+        if plane.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"plane: expected uint32 or int32, got {plane.dtype}")
+        _chk(plane, plane.dtype, "plane")
+        if tuple(plane.shape) != (crop_h, crop_w):
+            raise ValueError(f"plane: shape {tuple(plane.shape)} != ({crop_h}, {crop_w})")
+    _chk(cr_ws, torch.uint8, "cr_ws", class_regions_workspace_bytes(B, crop_h, crop_w, bool(conf)))
+    _chk(ws, torch.uint8, "ws", zone_presence_workspace_bytes(B, crop_h, crop_w, tracks))
+    S, pred, last, qq = 0, 0, 0, PR.quantize(PR.DEFAULT_MIN_SHARE)
+    if tracks:
+        counts = [int(c) for c in counts]
+        if not counts or min(counts) < 0 or sum(counts) != B or len(counts) > 65535:
+            raise ValueError(f"zone_presence: bad layout {counts} for a batch of {B}")
+        S, qq = len(counts), int(q)
+        if not 1 <= qq <= 1024:
+            raise ValueError(f"zone_presence: q {q} outside 1 .. 1024")
+        _chk(tws, torch.uint8, "tws", region_tracks_workspace_bytes(B, crop_h, crop_w, K))
+        _chk(state, torch.uint8, "state")
+        if state.numel() != zone_presence_state_bytes(S, K, R):
+            raise ValueError(f"state: {state.numel()} bytes != {zone_presence_state_bytes(S, K, R)}")
+        _chk(tables, torch.int32, "tables")
+        if tables.numel() != 2 * B + S:
+            raise ValueError(f"tables: {tables.numel()} words != 2 * {B} + {S}")
+        pred, last = _ptr(tables), _ptr(tables) + 8 * B
+    for t in (out, plane, cr_ws, ws, tws, state, tables):
+        if t is not None and t.device != rows.device:
+            raise ValueError("zone_presence: the buffers are on different devices")
+    _hip_mod().zone_presence(_ptr(rows), _ptr(cr_ws), _ptr(tws), _ptr(plane), B, crop_h, crop_w, K, R,
+                             rw, _ptr(out), _ptr(ws), _ptr(state), pred, last, S, qq, _stream())
+    _dbg('zone_presence')
+    return out
+
+
+def zone_presence_copy_to_host(src: torch.Tensor, dst: torch.Tensor, K: int, U: int) -> torch.Tensor:
+    """``zone_presence``'s out [B, 4 + U K] -> dst, the same layout in PINNED host memory: per
+    frame only the header and the ``n`` entries, by a kernel on the current stream."""
+    if not src.is_cuda or dst.is_cuda or not dst.is_pinned():
+        raise ValueError("zone_presence_copy_to_host: CUDA source, pinned host destination")
+    if not (src.is_contiguous() and dst.is_contiguous()) or src.element_size() != 4 or dst.element_size() != 4:
+        raise ValueError("zone_presence_copy_to_host: contiguous tensors of 4-byte words required")
+    if src.dim() != 2 or tuple(src.shape) != tuple(dst.shape) or src.shape[1] != 4 + int(U) * int(K):
+        raise ValueError(f"zone_presence_copy_to_host: shapes {tuple(src.shape)}, {tuple(dst.shape)} != "
+                         f"[B, 4 + {U} * {K}]")
+    _hip_mod().zone_presence_copy_used(src.data_ptr(), dst.data_ptr(), src.shape[0], int(K), int(U), _stream())
+    return dst
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

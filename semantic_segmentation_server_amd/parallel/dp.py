@@ -214,6 +214,13 @@ class DataParallelPipeline:
                 raise ValueError("serve_zones is not supported in a multi-rank group (world size "
                                  f"{ctx.world}): zone occupancy is not gathered across ranks; run one "
                                  "GPU, or the supervised server (independent workers)")
+        # --serve_presence: the same for each step's presence words ([B, 4 + U K]); only the
+        # header and the n entries of each frame are written to pinned memory, by a kernel like
+        # the records' (_d2h_presence), not a Tensor.copy_ ("Zone occupancy").
+        # A multi-rank group has refused --serve_regions above
+        self.presence_rows = int(getattr(engine, "presence_rows", 0) or 0)
+        self.presence_unit = int(getattr(engine, "presence_unit", 0) or 0)
+        self.presence_tracks = bool(getattr(engine, "presence_tracks", False))
         # lag L >= 1: step k collects step k-L's records, with L + 1 staging slots (so L + 1
         # steps can be in flight on a slot-parallel engine); SSA_PIPE_LAG overrides a
         # non-zero lag, else the engine may ask for more depth (slot-parallel: 2)
@@ -302,6 +309,9 @@ class DataParallelPipeline:
         self.local_zones = [torch.zeros((self.B, self.zone_words), dtype=torch.int32,
                                         pin_memory=self.cuda) for _ in range(NS)] \
             if self.zone_rows else None
+        self.local_presence = [torch.zeros((self.B, 4 + self.presence_unit * self.region_cap), dtype=torch.int32,
+                                           pin_memory=self.cuda) for _ in range(NS)] \
+            if self.presence_rows else None
         if gather == "host" and ctx.initialized:
             self.host_send = torch.empty((self.B, self.comb_width), dtype=torch.float32)
             self.host_gather = torch.empty((ctx.world, self.B, self.comb_width), dtype=torch.float32)
@@ -531,9 +541,13 @@ class DataParallelPipeline:
             if self.mask_cap and self.hub is not None and hasattr(self.hub, "push_masks"):
                 self.hub.push_masks(self.engine.host_masks(labels), self._node_meta(fids, strm, tss))
             if self.region_cap and self.hub is not None and hasattr(self.hub, "push_regions"):
-                self.hub.push_regions(self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None),
-                                                               *([strm] if self.track else [])),
-                                      self._node_meta(fids, strm, tss), **self._region_kw)
+                hreg = self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None),
+                                                *([strm] if self.track else []))
+                self.hub.push_regions(hreg, self._node_meta(fids, strm, tss), **self._region_kw)
+                if self.presence_rows and hasattr(self.hub, "push_presence"):
+                    self.hub.push_presence(self.engine.host_presence(labels, hreg, strm if self.track else None),
+                                           self._node_meta(fids, strm, tss), self.presence_unit,
+                                           tracks=self.presence_tracks)
             if self.zone_rows and self.hub is not None and hasattr(self.hub, "push_zones"):
                 self.hub.push_zones(self.engine.host_zones(labels, getattr(self.engine, "conf_plane", None)),
                                     self._node_meta(fids, strm, tss), conf=self.zone_conf)
@@ -543,6 +557,7 @@ class DataParallelPipeline:
         mask = self.engine.mask_packed if self.mask_cap else None
         regions = self.engine.region_packed if self.region_cap else None
         zones = self.engine.zone_packed if self.zone_rows else None
+        presence = self.engine.presence_packed if self.presence_rows else None
         slot = self._rslot
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
@@ -559,6 +574,8 @@ class DataParallelPipeline:
                         self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
                     if zones is not None:
                         self._d2h(zones, self.local_zones[slot])
+                    if presence is not None:
+                        self._d2h_presence(presence, self.local_presence[slot])
                 ev = self._rec_ev[slot]  # per record slot: collected before the slot is reused
                 ev.record(rs)
             else:
@@ -569,6 +586,8 @@ class DataParallelPipeline:
                     self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
                 if zones is not None:
                     self._d2h(zones, self.local_zones[slot])
+                if presence is not None:
+                    self._d2h_presence(presence, self.local_presence[slot])
                 if self.cuda:
                     ev = self._rec_ev[slot]
                     ev.record(fast_cuda.current_stream(self.dev_index))
@@ -600,6 +619,8 @@ class DataParallelPipeline:
                 self.local_regions[slot].copy_(regions, non_blocking=self.cuda)
             if zones is not None:
                 self._d2h(zones, self.local_zones[slot])
+            if presence is not None:
+                self._d2h_presence(presence, self.local_presence[slot])
             # every rank (non-root ones too) records the step and goes through the lag
             # throttle: meta_host[slot] is rewritten only after the step that last used it
             # has been collected, i.e. after its H2D copy ran (VERDICT r3 Weak #4: non-root
@@ -644,6 +665,16 @@ class DataParallelPipeline:
                 and getattr(self.engine, "backend", "hip") == "hip":
             from ..ops import hip_ops
             hip_ops.mask_rle_copy_to_host(src, dst)
+        else:
+            dst.copy_(src, non_blocking=self.cuda)
+
+    def _d2h_presence(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+        """Presence words -> pinned host buffer on the current stream, as ``_d2h_mask``: the HIP
+        build copies only each frame's header and its n entries."""
+        if self.cuda and src.is_cuda and dst.is_pinned() and src.is_contiguous() \
+                and getattr(self.engine, "backend", "hip") == "hip":
+            from ..ops import hip_ops
+            hip_ops.zone_presence_copy_to_host(src, dst, self.region_cap, self.presence_unit)
         else:
             dst.copy_(src, non_blocking=self.cuda)
 
@@ -816,6 +847,9 @@ class DataParallelPipeline:
         if self.region_cap and hasattr(self.hub, "push_regions"):
             self.hub.push_regions(self.local_regions[slot].numpy(), meta, **self._region_kw)
         self._push_zones(slot, meta)
+        if self.presence_rows and hasattr(self.hub, "push_presence"):
+            self.hub.push_presence(self.local_presence[slot].numpy(), meta, self.presence_unit,
+                                   tracks=self.presence_tracks)
 
     def _push_zones(self, slot: int, meta: np.ndarray) -> None:
         """The same for the collected step's zone words, if the hub takes zones."""

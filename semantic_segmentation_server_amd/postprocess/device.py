@@ -22,8 +22,18 @@ class DevicePostprocess:
                  bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
                  region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False,
                  track_streams: int = 0, track_q: int = 0, zone_rows: int = 0, zone_classes: int = 0,
-                 zone_conf: bool = False):
+                 zone_conf: bool = False, presence_rows: int = 0, presence_q: int = 0):
         self.device = device
+        # presence_rows (--serve_presence): R of the zone-presence kernels (zone_presence.hip),
+        # the zone rows; 0: no kernel, no buffer, no launch. They follow the region (and track)
+        # and zone kernels, read the zone plane of the crop, and with track_streams carry a
+        # dwell state per stream beside the track state (reset_tracks clears both)
+        self.presence_rows, self.presence_q = int(presence_rows), int(presence_q)
+        if self.presence_rows and not (region_cap and self.presence_rows == int(zone_rows)):
+            raise ValueError("DevicePostprocess: presence_rows needs region_cap and equals zone_rows")
+        self._presence_bufs: Dict[tuple, tuple] = {}
+        self._presence_state: Dict[tuple, torch.Tensor] = {}
+        self.last_presence = None
         # zone_rows (--serve_zones): R = 1 + the user zones of the zone-occupancy kernel
         # (zone_stats.hip), zone_classes its C; 0: no kernel, no buffer, no launch. zone_conf:
         # run() takes the confidence plane and the rows have the sum_conf block. The zone plane
@@ -177,19 +187,41 @@ class DevicePostprocess:
                 dtype=torch.uint8, device=self.device)
         return self._track_bufs[key] + (self._track_state[skey],)
 
+    def presence_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(workspace, [B, 4 + U region_cap] int32 presence words, the streams' carried dwell
+        state or None without tracking) of the zone-presence kernels: static and shared like
+        ``zone_buffers``; the state belongs to the crop alone. Every run writes every word."""
+        key = (B, crop_w, crop_h)
+        tr = bool(self.track_streams)
+        if key not in self._presence_bufs:
+            from . import presence as PR
+            PR.check_geometry(crop_w, crop_h, self.presence_rows - 1, self.region_cap)
+            ws = torch.zeros(hip_ops.zone_presence_workspace_bytes(B, crop_h, crop_w, tr),
+                             dtype=torch.uint8, device=self.device)
+            words = torch.zeros((B, PR.frame_words(self.region_cap, self.presence_rows, tr)),
+                                dtype=torch.int32, device=self.device)
+            self._presence_bufs[key] = (ws, words)
+        skey = (crop_w, crop_h)
+        if tr and skey not in self._presence_state:
+            self._presence_state[skey] = torch.zeros(
+                hip_ops.zone_presence_state_bytes(self.track_streams, self.region_cap, self.presence_rows),
+                dtype=torch.uint8, device=self.device)
+        return self._presence_bufs[key] + (self._presence_state.get(skey),)
+
     def reset_tracks(self) -> None:
-        """Forget every stream's carried state (ids start again at 1), once the device is idle."""
+        """Forget every stream's carried state (ids start again at 1, dwells at 0), once the
+        device is idle."""
         if not self._track_state:
             return
         torch.cuda.synchronize(self.device)
-        for st in self._track_state.values():
+        for st in list(self._track_state.values()) + list(self._presence_state.values()):
             st.zero_()
         torch.cuda.synchronize(self.device)
 
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
             out: torch.Tensor = None, mask_out: torch.Tensor = None,
             region_out: torch.Tensor = None, conf: torch.Tensor = None,
-            zone_out: torch.Tensor = None) -> torch.Tensor:
+            zone_out: torch.Tensor = None, presence_out: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
         shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
@@ -203,7 +235,10 @@ class DevicePostprocess:
         the frames of ``labels`` are the next ones of their streams, laid out by ``track_counts``.
         With ``zone_rows`` the zone occupancy comes last on the same stream, into
         ``zone_buffers(B)`` or ``zone_out`` ([B, 4 + R C] int32 rows, [B, 4 + 2 R C] with
-        ``zone_conf``, which reads ``conf`` too); ``last_zones`` is the buffer written."""
+        ``zone_conf``, which reads ``conf`` too); ``last_zones`` is the buffer written. With
+        ``presence_rows`` the zone presence of the regions follows, into ``presence_buffers(B)`` or
+        ``presence_out`` ([B, 4 + U region_cap] int32 rows); ``last_presence`` is the buffer
+        written."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
@@ -258,6 +293,19 @@ class DevicePostprocess:
                                crop_w=crop_w, R=self.zone_rows, C=self.zone_classes, plane=plane,
                                conf=conf if self.zone_conf else None)
             self.last_zones = words
+        if self.presence_rows:
+            pws, words, pstate = self.presence_buffers(B, crop_w, crop_h)
+            if presence_out is not None:
+                words = presence_out
+            kw = {}
+            if self.track_streams:
+                tws, tables, _, _ = self.track_buffers(B, crop_w, crop_h)
+                kw = dict(tws=tws, state=pstate, tables=tables, counts=self.track_counts(B),
+                          q=self.presence_q)
+            hip_ops.zone_presence(self.last_regions, words, pws, rws, B=B, crop_h=crop_h, crop_w=crop_w,
+                                  K=self.region_cap, R=self.presence_rows, plane=plane,
+                                  conf=self.region_conf, **kw)
+            self.last_presence = words
         return rec
 
     def fetch(self, rec: torch.Tensor, frame_ids: Sequence[int], ts: Sequence[float],
@@ -284,3 +332,4 @@ class DevicePostprocess:
 
     fetch_regions = fetch_masks  # the same: a uint32 row per frame with a 4-word header
     fetch_zones = fetch_masks
+    fetch_presence = fetch_masks

@@ -4,8 +4,9 @@ and the static outputs they write (``labels``; ``post``: packed records or None;
 record wider with --track_regions, whose per-stream state lives in the engine's one
 DevicePostprocess: the post-processing graphs of all slots advance it in replay order); ``conf``: the
 --serve_confidence plane of ``labels``, which the post-processing graph reads, or None;
-``zones``: --serve_zones zone words, written by the last kernels of the post-processing chain, or
-None).
+``zones``: --serve_zones zone words, or None; ``presence``: --serve_presence presence words,
+written by the last kernels of the post-processing chain (their dwell state lives beside the
+track state), or None).
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
 may be refilled (None: the model ran on the caller's stream).
 
@@ -56,6 +57,7 @@ class WholeStep:
         self.graph, (self.labels, self.post, self.mask, self.regions, self.conf) = _graph(
             lambda: eng._step_all(frames, bgr))
         self.zones = eng._step_zones  # --serve_zones: the zone words the graph writes, or None
+        self.presence = eng._step_presence  # --serve_presence: the same
 
     def replay(self) -> None:
         self.graph.replay()
@@ -92,7 +94,8 @@ class SplitStep:
         else:
             self.model, _ = _graph(infer)
         self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab, conf=cf))
-        self.zones = eng.device_zones()  # --serve_zones: the last kernels of the chain, or None
+        self.zones = eng.device_zones()  # --serve_zones, or None
+        self.presence = eng.device_presence()  # --serve_presence: the last kernels of the chain, or None
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
     def replay(self) -> None:
@@ -160,6 +163,10 @@ class PartsStep:
             from ..postprocess import zones as ZN
             self.zones = zn = torch.zeros((B, ZN.frame_words(eng.zone_rows, eng.zone_classes, eng.zone_conf)),
                                           dtype=torch.int32, device=dev)
+        self.presence = pr = None
+        if eng.presence_rows:
+            self.presence = pr = torch.zeros((B, 4 + eng.presence_unit * eng.region_cap), dtype=torch.int32,
+                                             device=dev)
         parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
                                                 eng.lut_x, eng.lut_y, out=lab[sl], part=i,
                                                 conf_out=cf[sl] if cf is not None else None),
@@ -167,7 +174,8 @@ class PartsStep:
                                                  mask_out=mask[sl] if mask is not None else None,
                                                  region_out=reg[sl] if reg is not None else None,
                                                  conf=cf[sl] if cf is not None else None,
-                                                 zone_out=zn[sl] if zn is not None else None))
+                                                 zone_out=zn[sl] if zn is not None else None,
+                                                 presence_out=pr[sl] if pr is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)
         for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
             run()

@@ -180,6 +180,26 @@ class Engine:
             self.track_q = TK.quantize(cfg.track_min_overlap)
             self._trackers = TK.Trackers(self.track_q)
             self.region_words += 2
+        # --serve_presence: pixel overlap of every stored region with every zone row and, with
+        # tracks, the dwell of its track in each (postprocess/presence.py). presence_rows: R (0 =
+        # off: no kernel, no buffer); presence_packed / presence: as zone_packed / zones,
+        # [B, 4 + U region_cap] words. The device dwell state lives in the one DevicePostprocess
+        # beside the track state; the host paths keep a StreamDwell per stream id
+        self.presence_rows, self.presence_q, self.presence_unit = 0, 0, 0
+        self.presence_tracks = False
+        self._dwells = None
+        if getattr(cfg, "serve_presence", False):
+            if not (cfg.serve_regions and serve_zones):
+                raise ValueError("--serve_presence requires --serve_regions and --serve_zones")
+            from ..postprocess import presence as PR
+            self.presence_rows, self.presence_tracks = self.zone_rows, self.track_regions
+            self.presence_q = PR.quantize(cfg.presence_min_share)
+            self.presence_unit = PR.unit(self.presence_rows, self.presence_tracks)
+            PR.check_geometry(self.W, self.H, self.presence_rows - 1, self.region_cap)  # every crop is within
+            self._dwells = PR.Dwells()
+        self.presence_packed: Optional[torch.Tensor] = None
+        self.presence: Optional[np.ndarray] = None
+        self._step_presence = None  # the presence words of the step _step_all issued last
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -300,19 +320,23 @@ class Engine:
                      mask_out: Optional[torch.Tensor] = None,
                      region_out: Optional[torch.Tensor] = None,
                      conf: Optional[torch.Tensor] = None,
-                     zone_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        return self._post_and_mask(labels, out, mask_out, region_out, conf, zone_out)[0]  # the records alone
+                     zone_out: Optional[torch.Tensor] = None,
+                     presence_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self._post_and_mask(labels, out, mask_out, region_out, conf, zone_out,
+                                   presence_out)[0]  # the records alone
 
     def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                        mask_out: Optional[torch.Tensor] = None,
                        region_out: Optional[torch.Tensor] = None,
                        conf: Optional[torch.Tensor] = None,
-                       zone_out: Optional[torch.Tensor] = None):
+                       zone_out: Optional[torch.Tensor] = None,
+                       presence_out: Optional[torch.Tensor] = None):
         """(device records of ``labels``, with ``mask_cap`` their run-length masks else None,
         with ``region_cap`` their class regions else None), each right after the other on the
         same stream: one captured graph, a chain, holds all. ``conf``: the confidence plane of
         ``labels`` (``serve_confidence``), summed per region. With ``zone_rows`` the zone
-        occupancy ends the chain; its words are ``device_zones()``."""
+        occupancy ends the chain; its words are ``device_zones()``. With ``presence_rows`` the
+        zone presence follows it; its words are ``device_presence()``."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -326,10 +350,14 @@ class Engine:
                                                region_conf=self.serve_confidence,
                                                track_streams=self.track_streams, track_q=self.track_q,
                                                zone_rows=self.zone_rows, zone_classes=self.zone_classes,
-                                               zone_conf=self.zone_conf)
+                                               zone_conf=self.zone_conf,
+                                               presence_rows=self.presence_rows,
+                                               presence_q=self.presence_q)
             if self.zone_rows > 1:
                 self._hip_post.set_zone_plane(self.zone_plane)
         kw = {"zone_out": zone_out} if self.zone_rows else {}
+        if self.presence_rows:
+            kw["presence_out"] = presence_out
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
                                  mask_out=mask_out, region_out=region_out, conf=conf, **kw)
         return (rec, self._hip_post.last_mask if self.mask_cap else None,
@@ -338,6 +366,11 @@ class Engine:
     def device_zones(self) -> Optional[torch.Tensor]:
         """The zone words the device post-processing wrote last (None without ``zone_rows``)."""
         return self._hip_post.last_zones if self.zone_rows and self._hip_post is not None else None
+
+    def device_presence(self) -> Optional[torch.Tensor]:
+        """The presence words the device post-processing wrote last (None without
+        ``presence_rows``)."""
+        return self._hip_post.last_presence if self.presence_rows and self._hip_post is not None else None
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
@@ -380,6 +413,8 @@ class Engine:
             return
         self._trackers.reset()
         self._track_ids = {}
+        if self._dwells is not None:
+            self._dwells.reset()
         if self._hip_post is not None:
             self._hip_post.reset_tracks()
 
@@ -426,6 +461,27 @@ class Engine:
                       conf=None if conf is None else conf[b], out=out[b], rows=self.zone_rows)
         return out
 
+    def host_presence(self, labels, regions, streams=None) -> np.ndarray:
+        """uint32 [B, 4 + U cap] presence words of host label maps by the numpy definition
+        (postprocess/presence.py): the CPU path, and a GPU without device post-processing.
+        ``regions``: the region words of the same frames (``host_regions``: with ``track_regions``
+        their track ids and ages are read, and the frames advance the StreamDwell of their
+        ``streams``, as there)."""
+        from ..postprocess import presence as PR
+        from ..postprocess import regions as RG
+        lab = labels.cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+        reg = regions.cpu().numpy() if isinstance(regions, torch.Tensor) else np.asarray(regions)
+        tr = self.presence_tracks
+        if tr:
+            streams = self.track_layout(lab.shape[0]) if streams is None else _per_frame(streams, lab.shape[0])
+        out = np.zeros((lab.shape[0], PR.frame_words(self.region_cap, self.presence_rows, tr)), np.uint32)
+        for b in range(lab.shape[0]):
+            tab = RG.decode(reg[b], conf=self.serve_confidence, tracks=True) if tr else None
+            PR.encode(lab[b], self.zone_plane, self.crop_w, self.crop_h, self.region_mask,
+                      self.region_min_pixels, self.region_cap, self.presence_rows, self.presence_q,
+                      tab=tab, dwell=self._dwells.of(streams[b]) if tr else None, out=out[b])
+        return out
+
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
         """One eager step: (labels, packed records or None, mask run words or None, region
         words or None)."""
@@ -437,6 +493,7 @@ class Engine:
         if self._use_device_post():
             out = (labels, *self._post_and_mask(labels, conf=conf), conf)
             self._step_zones = self.device_zones()
+            self._step_presence = self.device_presence()
             return out
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
@@ -446,12 +503,15 @@ class Engine:
             if host and self.region_cap else None
         self._step_zones = torch.from_numpy(self.host_zones(labels, conf).view(np.int32)) \
             if host and self.zone_rows else None
+        self._step_presence = torch.from_numpy(self.host_presence(labels, regions).view(np.int32)) \
+            if host and self.presence_rows else None
         post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
         return labels, post, mask, regions, conf
 
     def _step_device(self, frames: torch.Tensor):
         labels, post, self.mask_packed, self.region_packed, self.conf_plane = self._step_all(frames)
         self.zone_packed = self._step_zones
+        self.presence_packed = self._step_presence
         return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
@@ -588,6 +648,7 @@ class Engine:
         self.mask_packed, self.region_packed, self.last_consumed = step.mask, step.regions, step.consumed
         self.conf_plane = step.conf
         self.zone_packed = step.zones
+        self.presence_packed = step.presence
         return step.labels, step.post
 
     # ------------------------------------------------------------ post/host
@@ -646,6 +707,8 @@ class Engine:
                 self.regions = self.host_regions(labels, self.conf_plane, streams)
             if self.zone_rows:
                 self.zones = self.host_zones(labels, self.conf_plane)
+            if self.presence_rows:
+                self.presence = self.host_presence(labels, self.regions, streams)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         if self._use_device_post():
@@ -666,6 +729,8 @@ class Engine:
                     self.regions = self._hip_post.fetch_regions(self.region_packed)
                 if self.zone_rows:
                     self.zones = self._hip_post.fetch_zones(self.zone_packed)
+                if self.presence_rows:
+                    self.presence = self._hip_post.fetch_presence(self.presence_packed)
             else:
                 recs = None
         self.stream.synchronize()
@@ -675,6 +740,8 @@ class Engine:
             self.regions = self.host_regions(labels, self.conf_plane, streams)
         if self.zone_rows and post is None:
             self.zones = self.host_zones(labels, self.conf_plane)
+        if self.presence_rows and post is None:
+            self.presence = self.host_presence(labels, self.regions, streams)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

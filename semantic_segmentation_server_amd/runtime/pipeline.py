@@ -158,6 +158,11 @@ class Producer(threading.Thread):
                     if zones is not None and hasattr(self.hub, "push_zones"):  # --serve_zones
                         self.hub.push_zones(zones, np.array([ids, streams, ts], np.float64).T,
                                             conf=bool(getattr(self.engine, "zone_conf", False)))
+                    presence = getattr(self.engine, "presence", None)
+                    if presence is not None and hasattr(self.hub, "push_presence"):  # --serve_presence
+                        self.hub.push_presence(presence, np.array([ids, streams, ts], np.float64).T,
+                                               self.engine.presence_unit,
+                                               tracks=bool(self.engine.presence_tracks))
                 self.metrics.observe("objects_per_frame", len(recs) / max(1, len(ids)))
                 self.metrics.observe("buffer_depth", self.hub.depth)
                 dt = (time.perf_counter() - t0) * 1e3

@@ -154,6 +154,14 @@ class StoredZones(NamedTuple):
     conf: bool = False  # the words end in the sum_conf block (--serve_confidence)
 
 
+class StoredPresence(NamedTuple):
+    """A stream's latest zone presence: the words are the hub's own copy."""
+    frame_id: int
+    ts: float
+    words: np.ndarray  # uint32[4 + U * entries] (postprocess/presence.py)
+    tracks: bool = False  # the entries carry track_id and the dwell block (--track_regions)
+
+
 def latest_rows(rows: np.ndarray, meta: np.ndarray, unit: int = 1):
     """Of a collected batch of uint32 rows with a 4-word header whose word 0 counts the
     payload entries (``unit`` words each; run words: 1, region words: 6, or 7 with
@@ -184,6 +192,7 @@ class ResultHub:
         self._masks: Dict[int, StoredMask] = {}
         self._regions: Dict[int, StoredRegions] = {}
         self._zones: Dict[int, StoredZones] = {}
+        self._presence: Dict[int, StoredPresence] = {}
 
     def get(self, stream: int) -> Optional[ResultBuffer]:
         """The stream's buffer, or None for a stream id the hub does not serve (RPC
@@ -288,6 +297,28 @@ class ResultHub:
         first one."""
         with self._lock:
             return self._zones.get(int(stream))
+
+    # ---- zone presence (--serve_presence): the LATEST presence words per stream
+    def put_presence(self, stream: int, frame_id: int, ts: float, words: np.ndarray,
+                     tracks: bool = False) -> None:
+        """Store a COPY of ``words`` (header + entries, postprocess/presence.py) as the stream's
+        latest zone presence. ``tracks``: the entries have the dwell block."""
+        p = StoredPresence(int(frame_id), float(ts), np.array(words, dtype=np.uint32, copy=True), bool(tracks))
+        with self._lock:
+            self._presence[int(stream)] = p
+
+    def push_presence(self, rows: np.ndarray, meta: np.ndarray, unit: int, tracks: bool = False) -> None:
+        """As ``push_regions`` for [F, 4 + U K] presence words with entries of ``unit`` = U words:
+        of several frames of one stream only the last is copied, and only its ``4 + U n`` used
+        words."""
+        for st, fid, ts, words in latest_rows(rows, meta, int(unit)):
+            self.put_presence(st, fid, ts, words, tracks)
+
+    def presence(self, stream: int) -> Optional["StoredPresence"]:
+        """The stream's latest zone presence (frame_id, ts, words, tracks), or None before the
+        first one."""
+        with self._lock:
+            return self._presence.get(int(stream))
 
     @property
     def depth(self) -> int:

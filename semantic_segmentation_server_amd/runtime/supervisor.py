@@ -282,8 +282,10 @@ class _RingHub:
     the latest masks / regions to the incarnation's channels)."""
 
     def __init__(self, ring: _RecordRing, masks: Optional[_WordChannel] = None,
-                 regions: Optional[_WordChannel] = None, zones: Optional[_WordChannel] = None):
+                 regions: Optional[_WordChannel] = None, zones: Optional[_WordChannel] = None,
+                 presence: Optional[_WordChannel] = None):
         self.ring = ring
+        self.presence_ch = presence
         self.masks = masks
         self.region_ch = regions
         self.zone_ch = zones
@@ -318,6 +320,14 @@ class _RingHub:
         for st, fid, ts, words in latest_rows(rows, meta, self.zone_ch.unit):
             self.zone_ch.write(st, fid, ts, words)
 
+    def push_presence(self, rows: np.ndarray, meta: np.ndarray, unit: int, tracks: bool = False) -> None:
+        """As ResultHub.push_presence: a frame's words are n entries (word 0) of the channel's
+        unit U (from the one config, like the zone names and q on the parent's side)."""
+        if self.presence_ch is None:
+            return
+        for st, fid, ts, words in latest_rows(rows, meta, self.presence_ch.unit):
+            self.presence_ch.write(st, fid, ts, words)
+
 
 def _fault_for(spec: Optional[str], rank: int, incarnation: int):
     """(kind, step) of the fault injected into this worker incarnation, or None."""
@@ -333,7 +343,8 @@ def _fault_for(spec: Optional[str], rank: int, incarnation: int):
 
 def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnation: int,
                  max_steps: Optional[int], mask_name: Optional[str] = None,
-                 region_name: Optional[str] = None, zone_name: Optional[str] = None) -> None:
+                 region_name: Optional[str] = None, zone_name: Optional[str] = None,
+                 presence_name: Optional[str] = None) -> None:
     """Child process: rank ``rank``'s producer, reporting through the ring and ``q``."""
     logging.basicConfig(level=getattr(logging, cfg.log_level.upper(), logging.INFO),
                         format=f"%(asctime)s %(levelname)s worker{rank}: %(message)s")
@@ -349,6 +360,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     masks = _WordChannel(name=mask_name) if mask_name else None
     regions = _WordChannel(name=region_name) if region_name else None
     zones = _WordChannel(name=zone_name) if zone_name else None
+    presence = _WordChannel(name=presence_name) if presence_name else None
     metrics = Metrics()
     device = None
     if cfg.device != "cpu" and torch.cuda.is_available() and torch.cuda.device_count() > rank:
@@ -359,7 +371,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
                            cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank,
                            pixel_format=cfg.pixel_format)
                for s in range(S)]
-    prod = Producer(engine, sources, _RingHub(ring, masks, regions, zones), metrics, cfg.batch,
+    prod = Producer(engine, sources, _RingHub(ring, masks, regions, zones, presence), metrics, cfg.batch,
                     max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
 
@@ -412,6 +424,7 @@ class _Worker:
         self.masks: Optional[_WordChannel] = None
         self.regions: Optional[_WordChannel] = None
         self.zones: Optional[_WordChannel] = None
+        self.presence: Optional[_WordChannel] = None
         self.q = None
         self.up = False
         self.started = 0.0
@@ -460,6 +473,13 @@ class SupervisedServer:
             zl = ZN.load(cfg.zones) if cfg.zones else []
             ZN.check_geometry(cfg.input_size, cfg.input_size, len(zl), cfg.num_classes)
             self.zone_names = ZN.names(zl)
+        # --serve_presence: unit U and q come from the same config the workers read
+        self.presence_unit, self.presence_q = 0, 0
+        if getattr(cfg, "serve_presence", False):
+            from ..postprocess import presence as PR
+            PR.check_geometry(cfg.input_size, cfg.input_size, len(self.zone_names) - 1, int(cfg.max_regions))
+            self.presence_unit = PR.unit(len(self.zone_names), bool(cfg.track_regions))
+            self.presence_q = PR.quantize(cfg.presence_min_share)
         S.add_v1_servicer(S.SemanticSegmentationServicer(self.hub, labels, cfg.num_detections,
                                                          self.camera_res, metrics=self.metrics),
                           self.grpc_server)
@@ -470,7 +490,8 @@ class SupervisedServer:
                                                            serve_masks=cfg.serve_masks,
                                                            serve_regions=cfg.serve_regions,
                                                            model_size=(cfg.input_size, cfg.input_size),
-                                                           zone_names=self.zone_names),
+                                                           zone_names=self.zone_names,
+                                                           presence_q=self.presence_q),
                           self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
         self._ctx = mp.get_context("spawn")
@@ -521,11 +542,15 @@ class SupervisedServer:
         w.zones = _WordChannel(self.S, len(self.zone_names), w.rank * self.S,
                                unit=int(self.cfg.num_classes) * (2 if self.cfg.serve_confidence else 1)) \
             if self.zone_names else None
+        # presence words: n entries of U words each
+        w.presence = _WordChannel(self.S, int(self.cfg.max_regions), w.rank * self.S, unit=self.presence_unit) \
+            if self.presence_unit else None
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
                                          self.max_steps, w.masks.name if w.masks is not None else None,
                                          w.regions.name if w.regions is not None else None,
-                                         w.zones.name if w.zones is not None else None),
+                                         w.zones.name if w.zones is not None else None,
+                                         w.presence.name if w.presence is not None else None),
                                    daemon=True)
         w.proc.start()
         w.started = time.time()
@@ -568,6 +593,9 @@ class SupervisedServer:
         if w.zones is not None:
             for stream, fid, ts, words in w.zones.pull():
                 self.hub.put_zones(stream, fid, ts, words, conf=bool(self.cfg.serve_confidence))
+        if w.presence is not None:
+            for stream, fid, ts, words in w.presence.pull():
+                self.hub.put_presence(stream, fid, ts, words, tracks=bool(self.cfg.track_regions))
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
@@ -650,6 +678,9 @@ class SupervisedServer:
         if w.zones is not None:
             w.zones.close()
             w.zones = None
+        if w.presence is not None:
+            w.presence.close()
+            w.presence = None
         if w.q is not None:
             try:
                 w.q.close()

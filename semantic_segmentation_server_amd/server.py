@@ -65,7 +65,8 @@ class Server:
                                                    serve_masks=cfg.serve_masks,
                                                    serve_regions=cfg.serve_regions,
                                                    model_size=(cfg.input_size, cfg.input_size),
-                                                   zone_names=self._zone_names())
+                                                   zone_names=self._zone_names(),
+                                                   presence_q=int(getattr(self.engine, "presence_q", 0)))
         S.add_v1_servicer(self.v1, self.grpc_server)
         S.add_v2_servicer(self.v2, self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
