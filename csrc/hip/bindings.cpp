@@ -541,6 +541,26 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.attr("ZONE_PRESENCE_CHUNK") = zone_presence_chunk();
 
+  m.def("label_stable_state_bytes", &label_stable_state_bytes, py::arg("streams"), py::arg("crop_h"),
+        py::arg("crop_w"));
+  m.def("label_stable",
+        [](uintptr_t labels_in, uintptr_t labels_out, uintptr_t conf_in, uintptr_t conf_out,
+           uintptr_t state, uintptr_t tables, int B, int streams, int H, int W, int crop_h, int crop_w,
+           int frames, int g, uintptr_t stream) {
+          LabelStableParams p;
+          p.labels_in = P<const uint8_t>(labels_in); p.labels_out = P<uint8_t>(labels_out);
+          p.conf_in = P<const uint8_t>(conf_in); p.conf_out = P<uint8_t>(conf_out);
+          p.state = P<uint32_t>(state); p.tables = P<const int>(tables);
+          p.B = B; p.streams = streams; p.H = H; p.W = W; p.crop_h = crop_h; p.crop_w = crop_w;
+          p.frames = frames; p.g = g;
+          label_stable(p, S(stream));
+        },
+        py::arg("labels_in"), py::arg("labels_out"), py::arg("conf_in"), py::arg("conf_out"),
+        py::arg("state"), py::arg("tables"), py::arg("B"), py::arg("streams"), py::arg("H"),
+        py::arg("W"), py::arg("crop_h"), py::arg("crop_w"), py::arg("frames"), py::arg("g"),
+        py::arg("stream"));
+  m.attr("LABEL_STABLE_CHUNK") = label_stable_chunk();
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

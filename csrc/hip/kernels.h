@@ -465,4 +465,27 @@ void zone_presence(const ZonePresenceParams& p, hipStream_t s);
 // only the 4 + U n used words are written, by a kernel on stream s.
 void zone_presence_copy_used(const uint32_t* src, uint32_t* dst, int B, int K, int U, hipStream_t s);
 
+// ---- temporal label stabilisation (label_stable.hip; the definition is postprocess/stable.py) --
+// Ahead of every other post-processing kernel on the same stream: per stream and crop pixel a
+// label is held until a different one has been seen for `frames` (2 .. 255) consecutive frames;
+// with g > 0 an observation whose confidence code is below g is ignored. labels_out may be
+// labels_in and conf_out conf_in (in place); out of place every byte of the outputs is written,
+// pad pixels copied. conf_in / conf_out: both set or both null (then g == 0). The rows of a stream
+// are consecutive: tables = int32 first[streams] | count[streams], the rows of feeder.split_batch.
+// `state` is carried from run to run (label_stable_state_bytes: per stream a header word and
+// one word s | c << 8 | n << 16 | h << 24 per crop pixel; all zero: a reset). A stream with no
+// row touches nothing. H * W < 2^31.
+struct LabelStableParams {
+  const uint8_t* labels_in = nullptr;  // [B, H, W] (row stride W)
+  uint8_t* labels_out = nullptr;
+  const uint8_t* conf_in = nullptr;    // [B, H, W] or null
+  uint8_t* conf_out = nullptr;
+  uint32_t* state = nullptr;
+  const int* tables = nullptr;
+  int B = 0, streams = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, frames = 0, g = 0;
+};
+size_t label_stable_state_bytes(int streams, int crop_h, int crop_w);
+int label_stable_chunk();  // flat crop pixels per workgroup
+void label_stable(const LabelStableParams& p, hipStream_t s);
+
 }  // namespace ssa

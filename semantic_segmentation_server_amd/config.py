@@ -74,6 +74,8 @@ class Config:
     zones: Optional[str] = None            # zone file (JSON, postprocess/zones.py); None: the frame zone alone
     serve_presence: bool = False           # region x zone pixel overlap, per-track dwell (v2 GetZonePresence)
     presence_min_share: float = 0.5        # share of a region's pixels inside a zone that puts it inside, in (0, 1]
+    stable_labels: int = 0                 # hold each pixel's label until another is seen N frames in a row (0: off; 2 .. 255)
+    stable_min_confidence: float = 0.0     # ignore observations below this confidence, in [0, 1] (0: no gate)
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -112,6 +114,16 @@ class Config:
                              "the overlap of the class regions with the zones (v2 GetZonePresence)")
         if self.serve_presence and not 0.0 < float(self.presence_min_share) <= 1.0:
             raise ValueError(f"--presence_min_share {self.presence_min_share} outside (0, 1]")
+        if int(self.stable_labels) != 0 and not 2 <= int(self.stable_labels) <= 255:
+            raise ValueError(f"--stable_labels {self.stable_labels} outside 2 .. 255 (0: off)")
+        if not 0.0 <= float(self.stable_min_confidence) <= 1.0:
+            raise ValueError(f"--stable_min_confidence {self.stable_min_confidence} outside [0, 1]")
+        if float(self.stable_min_confidence) > 0.0 and not int(self.stable_labels):
+            raise ValueError(f"--stable_min_confidence {self.stable_min_confidence} requires "
+                             "--stable_labels: it gates the observations of the label stabilisation")
+        if float(self.stable_min_confidence) > 0.0 and not self.serve_confidence:
+            raise ValueError(f"--stable_min_confidence {self.stable_min_confidence} requires "
+                             "--serve_confidence: the gate reads the per-pixel confidence plane")
         if self.pixel_format != "bgr":
             if self.camera_width % 2:
                 raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
@@ -227,6 +239,14 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--presence_min_share", type=float, default=d.presence_min_share,
                    help="share of a region's pixels inside a zone from which the region counts as "
                         "inside it (0 < share <= 1)")
+    p.add_argument("--stable_labels", type=int, default=d.stable_labels, metavar="N",
+                   help="hold each pixel's label until a different label has been seen for N "
+                        "consecutive frames of its stream (2 .. 255), on the device ahead of all "
+                        "post-processing; records, masks, regions, tracks, zones and presence see "
+                        "the stabilised maps (0: off)")
+    p.add_argument("--stable_min_confidence", type=float, default=d.stable_min_confidence,
+                   help="with --stable_labels: ignore an observation whose confidence is below "
+                        "this (0 .. 1; 0: no gate); requires --serve_confidence")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

@@ -1565,6 +1565,87 @@ def zone_presence_copy_to_host(src: torch.Tensor, dst: torch.Tensor, K: int, U: 
     return dst
 
 
+def label_stable_state_bytes(streams, crop_h, crop_w) -> int:
+    return int(_hip_mod().label_stable_state_bytes(int(streams), int(crop_h), int(crop_w)))
+
+
+def label_stable_chunk() -> int:
+    """Flat crop pixels per workgroup of ``label_stable`` (the module's LABEL_STABLE_CHUNK)."""
+    return int(_hip_mod().LABEL_STABLE_CHUNK)
+
+
+def label_stable_tables(counts, device) -> torch.Tensor:
+    """The batch layout of ``label_stable`` on the device: int32 [first[S] | count[S]] from the
+    rows each stream owns (postprocess/stable.py ``batch_tables``)."""
+    from ..postprocess import stable as SB
+    return torch.from_numpy(SB.batch_tables(counts)).to(device)
+
+
+def label_stable(labels_in, labels_out, conf_in, conf_out, state, tables, *, counts, B, H, W, crop_h,
+                 crop_w, N, g=0):
+    """Temporal label stabilisation on the current stream (csrc/hip/label_stable.hip;
+    postprocess/stable.py is the definition): every pixel of ``labels_in[:, :crop_h, :crop_w]``
+    keeps its stream's stable label until another has been seen for ``N`` consecutive frames;
+    with ``g > 0`` observations whose code in ``conf_in`` is below ``g`` are ignored, and
+    ``conf_out`` gets the code with which the served label last won. ``labels_out`` may be
+    ``labels_in`` and ``conf_out`` ``conf_in`` (in place); out of place every byte of the outputs
+    is written. ``conf_in`` / ``conf_out``: both uint8 [B, H, W] or both None. ``counts``: the rows
+    each stream owns, consecutive, in stream order (B is their sum); ``tables``:
+    ``label_stable_tables(counts)``; ``state``: the streams' carried state, exactly
+    ``label_stable_state_bytes(len(counts), crop_h, crop_w)`` bytes (zero: a reset)."""
+    B, H, W, crop_h, crop_w, N, g = (int(v) for v in (B, H, W, crop_h, crop_w, N, g))
+    counts = [int(c) for c in counts]
+    if not counts or min(counts) < 0 or len(counts) > 65535:
+        raise ValueError(f"label_stable: bad layout {counts}")
+    S = len(counts)
+    if B < 1 or sum(counts) != B:
+        raise ValueError(f"label_stable: B {B} != the {sum(counts)} rows of counts {counts}")
+    if (conf_in is None) != (conf_out is None):
+        raise ValueError("label_stable: conf_in and conf_out are both given or both None")
+    for t, name in ((labels_in, "labels_in"), (labels_out, "labels_out"), (conf_in, "conf_in"),
+                    (conf_out, "conf_out")):
+        if t is None:
+            continue
+        _chk(t, torch.uint8, name)
+        if tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {H}, {W})")
+    if H * W >= 1 << 31:
+        raise ValueError(f"label_stable: {H} x {W} pixels, a plane has fewer than 2^31")
+    if not (1 <= crop_h <= H and 1 <= crop_w <= W):
+        raise ValueError(f"label_stable: crop {crop_h} x {crop_w} outside the {H} x {W} map")
+    if not 2 <= N <= 255:
+        raise ValueError(f"label_stable: N {N} outside 2 .. 255")
+    if not 0 <= g <= 255:
+        raise ValueError(f"label_stable: g {g} outside 0 .. 255")
+    if g > 0 and conf_in is None:
+        raise ValueError(f"label_stable: g {g} > 0 needs the conf planes")
+    _chk(state, torch.uint8, "state")
+    if state.numel() != label_stable_state_bytes(S, crop_h, crop_w):
+        raise ValueError(f"state: {state.numel()} bytes != {label_stable_state_bytes(S, crop_h, crop_w)}")
+    if state.data_ptr() % 4:
+        raise ValueError("state: not 4-byte aligned")
+    _chk(tables, torch.int32, "tables")
+    if tables.numel() != 2 * S:
+        raise ValueError(f"tables: {tables.numel()} words != 2 * {S}")
+    planes = [t for t in (labels_in, labels_out, conf_in, conf_out) if t is not None]
+    for t in planes[1:] + [state, tables]:
+        if t.device != labels_in.device:
+            raise ValueError("label_stable: the buffers are on different devices")
+    # an output that IS its input is the in-place form; anything else must not overlap
+    nbytes = B * H * W
+    for i, a in enumerate(planes):
+        for j in range(i + 1, len(planes)):
+            pa, pb = a.data_ptr(), planes[j].data_ptr()
+            if pa == pb and (i, j) in ((0, 1), (2, 3)):
+                continue
+            if pa < pb + nbytes and pb < pa + nbytes:
+                raise ValueError("label_stable: the planes overlap (only out == in may alias)")
+    _hip_mod().label_stable(_ptr(labels_in), _ptr(labels_out), _ptr(conf_in), _ptr(conf_out),
+                            _ptr(state), _ptr(tables), B, S, H, W, crop_h, crop_w, N, g, _stream())
+    _dbg('label_stable')
+    return labels_out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

@@ -197,6 +197,13 @@ class DataParallelPipeline:
                 raise ValueError("track_regions is not supported in a multi-rank group (world size "
                                  f"{ctx.world}): class regions and their tracks are not gathered "
                                  "across ranks; run one GPU, or the supervised server")
+        # --stable_labels: the label state of a stream lives in this rank's engine, with the
+        # batch layout of the tracks: the same checks and the same reset
+        self.stable = bool(getattr(engine, "stable_frames", 0))
+        if self.stable and ctx.initialized and ctx.world > 1:
+            raise ValueError("stable_labels is not supported in a multi-rank group (world size "
+                             f"{ctx.world}): the label state of a stream is not shared across ranks; "
+                             "run one GPU, or the supervised server")
         if self.region_cap and ctx.initialized and ctx.world > 1:
             raise ValueError("serve_regions is not supported in a multi-rank group (world size "
                              f"{ctx.world}): class regions are not gathered across ranks; run one "
@@ -370,7 +377,7 @@ class DataParallelPipeline:
         if self.cuda and hasattr(engine, "bind_inputs"):
             if engine.slot_parallel:
                 self._prime(int(os.environ.get("SSA_PIPE_PRIME", str(8 * self.nslots))))
-        if self.track:  # a pipeline starts: its first frames are the streams' first
+        if self.track or self.stable:  # a pipeline starts: its first frames are the streams' first
             engine.reset_tracks()
 
     def rccl_nranks(self) -> Optional[int]:
@@ -512,7 +519,7 @@ class DataParallelPipeline:
         strm = list(streams) if streams is not None else \
             [(self.ctx.rank * self.S + i % self.S) if nb == B else (i // B) * self.S + i % self.S
              for i in range(nb)]
-        if self.track:
+        if self.track or self.stable:
             if streams is None:  # the layout's own order, not round-robin
                 strm = [self.ctx.rank * self.S + s for s in self.engine.track_layout(B)]
             if self.cuda and self.engine._use_device_post():

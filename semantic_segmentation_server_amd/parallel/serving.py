@@ -246,6 +246,10 @@ def serve_distributed(cfg: Config) -> int:
         raise ValueError("--track_regions is not supported by the multi-rank server (class regions "
                          "and their tracks are not gathered across ranks); run one GPU, or the "
                          "supervised server (--gpus N without --no_supervise)")
+    if getattr(cfg, "stable_labels", 0) and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or cfg.gpus > 1):
+        raise ValueError("--stable_labels is not supported by the multi-rank server (the frames of a "
+                         "stream are spread over the ranks, its label state is not); run one GPU, "
+                         "or the supervised server (--gpus N without --no_supervise)")
     if cfg.serve_regions and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or cfg.gpus > 1):
         raise ValueError("--serve_regions is not supported by the multi-rank server (class regions "
                          "are not gathered across ranks); run one GPU, or the supervised "

@@ -22,8 +22,27 @@ class DevicePostprocess:
                  bins: int = 32, thr: int = 127, mask_cap: int = 0, region_cap: int = 0,
                  region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False,
                  track_streams: int = 0, track_q: int = 0, zone_rows: int = 0, zone_classes: int = 0,
-                 zone_conf: bool = False, presence_rows: int = 0, presence_q: int = 0):
+                 zone_conf: bool = False, presence_rows: int = 0, presence_q: int = 0,
+                 stable_frames: int = 0, stable_gate: int = 0, stable_streams: int = 0):
         self.device = device
+        # stable_frames (--stable_labels): N of the temporal label stabilisation
+        # (label_stable.hip), the first launch of run(): in place on the label maps (and on the
+        # confidence plane when one is passed), so every later kernel reads the stabilised
+        # planes. 0: no kernel, no buffer, no launch. stable_gate: the gate code of
+        # --stable_min_confidence. stable_streams: the streams whose frames this object sees,
+        # laid out like track_streams (and equal to it when both are on); their carried state
+        # lives beside the track state (reset_tracks clears it too)
+        self.stable_frames, self.stable_gate = int(stable_frames), int(stable_gate)
+        self.stable_streams = int(stable_streams)
+        if self.stable_frames:
+            from . import stable as SB
+            SB.check_params(self.stable_frames, self.stable_gate, True)
+            if self.stable_streams < 1:
+                raise ValueError("DevicePostprocess: stable_frames needs stable_streams")
+            if track_streams and int(track_streams) != self.stable_streams:
+                raise ValueError("DevicePostprocess: stable_streams differs from track_streams")
+        self._stable_tables: Dict[int, torch.Tensor] = {}
+        self._stable_state: Dict[tuple, torch.Tensor] = {}
         # presence_rows (--serve_presence): R of the zone-presence kernels (zone_presence.hip),
         # the zone rows; 0: no kernel, no buffer, no launch. They follow the region (and track)
         # and zone kernels, read the zone plane of the crop, and with track_streams carry a
@@ -167,7 +186,19 @@ class DevicePostprocess:
     def track_counts(self, B: int):
         """The rows of a batch of B frames that each stream owns (consecutive, in stream order)."""
         from ..runtime.feeder import split_batch
-        return split_batch(B, self.track_streams)
+        return split_batch(B, self.track_streams or self.stable_streams)
+
+    def stable_buffers(self, B: int, crop_w: int, crop_h: int):
+        """(layout table, the streams' carried state) of the label stabilisation; the state
+        belongs to the crop alone, like the track state."""
+        if B not in self._stable_tables:
+            self._stable_tables[B] = hip_ops.label_stable_tables(self.track_counts(B), self.device)
+        skey = (crop_w, crop_h)
+        if skey not in self._stable_state:
+            self._stable_state[skey] = torch.zeros(
+                hip_ops.label_stable_state_bytes(self.stable_streams, crop_h, crop_w),
+                dtype=torch.uint8, device=self.device)
+        return self._stable_tables[B], self._stable_state[skey]
 
     def track_buffers(self, B: int, crop_w: int, crop_h: int):
         """(scratch, layout tables, [B, 4 + (6 | 7 + 2) region_cap] int32 rows with tracks, the
@@ -209,12 +240,13 @@ class DevicePostprocess:
         return self._presence_bufs[key] + (self._presence_state.get(skey),)
 
     def reset_tracks(self) -> None:
-        """Forget every stream's carried state (ids start again at 1, dwells at 0), once the
-        device is idle."""
-        if not self._track_state:
+        """Forget every stream's carried state (ids start again at 1, dwells at 0, the next
+        frame's labels pass the stabilisation unchanged), once the device is idle."""
+        if not self._track_state and not self._stable_state:
             return
         torch.cuda.synchronize(self.device)
-        for st in list(self._track_state.values()) + list(self._presence_state.values()):
+        for st in (list(self._track_state.values()) + list(self._presence_state.values())
+                   + list(self._stable_state.values())):
             st.zero_()
         torch.cuda.synchronize(self.device)
 
@@ -238,10 +270,21 @@ class DevicePostprocess:
         ``zone_conf``, which reads ``conf`` too); ``last_zones`` is the buffer written. With
         ``presence_rows`` the zone presence of the regions follows, into ``presence_buffers(B)`` or
         ``presence_out`` ([B, 4 + U region_cap] int32 rows); ``last_presence`` is the buffer
-        written."""
+        written. With ``stable_frames`` the label stabilisation comes first, on the same stream
+        (the graph stays a chain): ``labels`` -- and ``conf``, when passed -- are overwritten in
+        place with the stabilised planes, which everything above then reads; the frames are the
+        next ones of their streams, laid out by ``track_counts``."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
+        if self.stable_frames:
+            if self.stable_gate and conf is None:
+                raise ValueError("DevicePostprocess.run: stable_gate needs the conf plane")
+            tables, state = self.stable_buffers(B, crop_w, crop_h)
+            hip_ops.label_stable(labels, labels, conf, conf, state, tables,
+                                 counts=self.track_counts(B), B=B, H=self.H, W=self.W,
+                                 crop_h=crop_h, crop_w=crop_w, N=self.stable_frames,
+                                 g=self.stable_gate)
         ws, rec = self._buffers(B)
         if out is not None:
             if (out.shape != rec.shape or out.dtype != rec.dtype or not out.is_contiguous()

@@ -6,7 +6,9 @@ DevicePostprocess: the post-processing graphs of all slots advance it in replay 
 --serve_confidence plane of ``labels``, which the post-processing graph reads, or None;
 ``zones``: --serve_zones zone words, or None; ``presence``: --serve_presence presence words,
 written by the last kernels of the post-processing chain (their dwell state lives beside the
-track state), or None).
+track state), or None). With --stable_labels the first launch of the post-processing chain
+rewrites ``labels`` (and ``conf``) in place with the stabilised planes, whose per-stream state
+lives there too: after the post-processing they are what the step hands out.
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
 may be refilled (None: the model ran on the caller's stream).
 

@@ -200,6 +200,22 @@ class Engine:
         self.presence_packed: Optional[torch.Tensor] = None
         self.presence: Optional[np.ndarray] = None
         self._step_presence = None  # the presence words of the step _step_all issued last
+        # --stable_labels N: every pixel keeps its label until another has been seen for N
+        # consecutive frames of its stream (postprocess/stable.py), ahead of all post-processing:
+        # the label maps (and the confidence plane) of a step ARE the stabilised ones. On the
+        # device the state of the stable_streams streams lives in the one DevicePostprocess
+        # beside the track state, with the same batch layout; the host paths keep a
+        # StreamStabilizer per stream id. 0: off -- no kernel, no buffer, nothing changes
+        self.stable_frames = int(getattr(cfg, "stable_labels", 0) or 0)
+        self.stable_gate, self.stable_streams, self._stabilizers = 0, 0, None
+        if float(getattr(cfg, "stable_min_confidence", 0.0) or 0.0) > 0.0 and not self.stable_frames:
+            raise ValueError("--stable_min_confidence requires --stable_labels")
+        if self.stable_frames:
+            from ..postprocess import stable as SB
+            self.stable_gate = SB.gate_code(cfg.stable_min_confidence)
+            SB.check_params(self.stable_frames, self.stable_gate, self.serve_confidence)
+            self.stable_streams = max(1, int(cfg.streams))
+            self._stabilizers = SB.Stabilizers(self.stable_frames, self.stable_gate)
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -352,7 +368,10 @@ class Engine:
                                                zone_rows=self.zone_rows, zone_classes=self.zone_classes,
                                                zone_conf=self.zone_conf,
                                                presence_rows=self.presence_rows,
-                                               presence_q=self.presence_q)
+                                               presence_q=self.presence_q,
+                                               stable_frames=self.stable_frames,
+                                               stable_gate=self.stable_gate,
+                                               stable_streams=self.stable_streams)
             if self.zone_rows > 1:
                 self._hip_post.set_zone_plane(self.zone_plane)
         kw = {"zone_out": zone_out} if self.zone_rows else {}
@@ -386,37 +405,60 @@ class Engine:
         return out
 
     def track_layout(self, B: int) -> List[int]:
-        """With ``track_regions``: the position (0 .. track_streams - 1) of the stream that owns
-        each row of a batch of B frames -- consecutive rows per stream, feeder.split_batch."""
+        """With ``track_regions`` or ``stable_frames``: the position (0 .. streams - 1) of the
+        stream that owns each row of a batch of B frames -- consecutive rows per stream,
+        feeder.split_batch."""
         from .feeder import split_batch
-        return [s for s, n in enumerate(split_batch(B, self.track_streams)) for _ in range(n)]
+        n_streams = self.track_streams or self.stable_streams
+        return [s for s, n in enumerate(split_batch(B, n_streams)) for _ in range(n)]
 
     def check_track_streams(self, streams, B: int) -> None:
-        """With ``track_regions`` on the device: raise unless the ``streams`` of a batch follow
-        the layout the tracking kernels were built for, with the same stream ids as before."""
-        if not self.track_regions:
+        """With ``track_regions`` or ``stable_frames`` on the device: raise unless the
+        ``streams`` of a batch follow the layout the stateful kernels were built for, with the
+        same stream ids as before."""
+        if not (self.track_regions or self.stable_frames):
             return
         got, want = _per_frame(streams, B), self.track_layout(B)
         ids = dict(self._track_ids)
         ok = len(got) == B and all(ids.setdefault(pos, st) == st for pos, st in zip(want, got))
         if not ok or len(set(ids.values())) != len(ids):
-            raise ValueError(f"--track_regions: the streams {got} of a batch of {B} frames do not follow "
-                             f"the layout {want} of --streams {self.track_streams} (consecutive rows "
-                             f"per stream, the same streams every step; so far {self._track_ids})")
+            flag = "--track_regions" if self.track_regions else "--stable_labels"
+            raise ValueError(f"{flag}: the streams {got} of a batch of {B} frames do not follow "
+                             f"the layout {want} of --streams {self.track_streams or self.stable_streams} "
+                             f"(consecutive rows per stream, the same streams every step; so far "
+                             f"{self._track_ids})")
         self._track_ids = ids
 
     def reset_tracks(self) -> None:
-        """Forget the tracks of every stream: the next frame's regions are all new, from id 1.
-        Called after warm-up and capture (their steps advance the state) and when a producer
-        or pipeline starts. Waits for the device."""
-        if not self.track_regions:
+        """Forget the tracks of every stream: the next frame's regions are all new, from id 1;
+        with ``stable_frames`` forget the stabilisation state too: the next frame's labels pass
+        unchanged. Called after warm-up and capture (their steps advance the state) and when a
+        producer or pipeline starts. Waits for the device."""
+        if not (self.track_regions or self.stable_frames):
             return
-        self._trackers.reset()
+        if self._trackers is not None:
+            self._trackers.reset()
+        if self._stabilizers is not None:
+            self._stabilizers.reset()
         self._track_ids = {}
         if self._dwells is not None:
             self._dwells.reset()
         if self._hip_post is not None:
             self._hip_post.reset_tracks()
+
+    def host_stable(self, labels: torch.Tensor, conf: Optional[torch.Tensor], streams=None):
+        """``stable_frames`` on the host paths (the CPU, and a GPU without device
+        post-processing): the frames advance the StreamStabilizer of their ``streams`` (default:
+        the layout positions of ``track_layout``) in row order, and ``labels`` (and ``conf``) are
+        overwritten in place with the stabilised planes, which are also returned."""
+        B = labels.shape[0]
+        streams = self.track_layout(B) if streams is None else _per_frame(streams, B)
+        lab, cf = self._stabilizers.step(labels.cpu().numpy(), None if conf is None else conf.cpu().numpy(),
+                                         self.crop_w, self.crop_h, streams)
+        labels.copy_(torch.from_numpy(lab))
+        if conf is not None:
+            conf.copy_(torch.from_numpy(cf))
+        return labels, conf
 
     def host_regions(self, labels, conf=None, streams=None) -> np.ndarray:
         """uint32 [B, 4 + 6 cap] region words of host label maps by the numpy definition
@@ -498,6 +540,8 @@ class Engine:
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
         host = not self.is_cuda
+        if host and self.stable_frames:  # a GPU's host path: run_device, once the maps exist
+            labels, conf = self.host_stable(labels, conf)
         mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
         regions = torch.from_numpy(self.host_regions(labels, conf).view(np.int32)) \
             if host and self.region_cap else None
@@ -562,6 +606,9 @@ class Engine:
         self.model_parts = int(os.environ.get("SSA_MODEL_PARTS", "1"))
         if self.track_regions and self.model_parts > 1:
             raise ValueError("--track_regions is not supported with SSA_MODEL_PARTS > 1: the parts of "
+                             "a batch are post-processed separately, not as one batch in stream order")
+        if self.stable_frames and self.model_parts > 1:
+            raise ValueError("--stable_labels is not supported with SSA_MODEL_PARTS > 1: the parts of "
                              "a batch are post-processed separately, not as one batch in stream order")
         self.model_streams = []
         self._bound = {b.data_ptr(): b for b in bufs}
@@ -633,7 +680,8 @@ class Engine:
         (with ``split_post``, the records are produced on ``result_stream``).
         """
         if not (self.cfg.graph and self.is_cuda):
-            return self._step_device(frames)
+            labels, post = self._step_device(frames)
+            return self._gpu_host_stable(labels), post
         step = self._bound_step(frames)
         if step is None:  # the engine's own static input buffer, for this batch size
             step, B = self._static_step, frames.shape[0]
@@ -649,7 +697,17 @@ class Engine:
         self.conf_plane = step.conf
         self.zone_packed = step.zones
         self.presence_packed = step.presence
-        return step.labels, step.post
+        return self._gpu_host_stable(step.labels), step.post
+
+    def _gpu_host_stable(self, labels: torch.Tensor) -> torch.Tensor:
+        """``stable_frames`` on a GPU without device post-processing: the label maps (and
+        ``conf_plane``) of the step just issued are stabilised on the host and written back in
+        place, once the stream has produced them; every consumer then reads those. Anything
+        else: ``labels`` as they are (the device chain has stabilised them already)."""
+        if self.stable_frames and self.is_cuda and not self._use_device_post():
+            torch.cuda.current_stream(self.device).synchronize()
+            self.host_stable(labels, self.conf_plane)
+        return labels
 
     # ------------------------------------------------------------ post/host
     def records_from_labels(self, labels: torch.Tensor, frame_ids: Sequence[int],
@@ -698,6 +756,9 @@ class Engine:
             frames = torch.from_numpy(np.ascontiguousarray(frames_host))
             with torch.no_grad():
                 labels, self.conf_plane = self._infer(frames)
+            if self.stable_frames:
+                labels, self.conf_plane = self.host_stable(labels, self.conf_plane,
+                                                           _per_frame(streams, len(frame_ids)))
             if self.debug is not None and self.debug.want():
                 self.debug.dump(self._host_bgr(frames_host[0]), labels[0].numpy(), self.crop_w, self.crop_h,
                                 _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

@@ -30,6 +30,9 @@ class StreamGroup:
         if getattr(cfg, "track_regions", False):
             raise ValueError("--track_regions is not supported by StreamGroup: its engines post-process "
                              "their streams with separate states; use one engine with --streams")
+        if getattr(cfg, "stable_labels", 0):
+            raise ValueError("--stable_labels is not supported by StreamGroup: its engines post-process "
+                             "their streams with separate states; use one engine with --streams")
         self.cfg = cfg
         self.device = device
         self.is_cuda = device.type == "cuda"

@@ -127,8 +127,8 @@ class Producer(threading.Thread):
     def run(self) -> None:
         failures = 0
         self.hub_clear()
-        if getattr(self.engine, "track_regions", False):  # a producer starts: ids from 1
-            self.engine.reset_tracks()
+        if getattr(self.engine, "track_regions", False) or getattr(self.engine, "stable_frames", 0):
+            self.engine.reset_tracks()  # a producer starts: ids from 1, no held labels
         if self._use_driver():
             self._run_driver()
             return
