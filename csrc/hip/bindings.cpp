@@ -541,6 +541,24 @@ PYBIND11_MODULE(_hip, m) {
   });
   m.attr("ZONE_PRESENCE_CHUNK") = zone_presence_chunk();
 
+  m.def("zone_events_state_bytes", &zone_events_state_bytes, py::arg("streams"), py::arg("K"),
+        py::arg("R"));
+  m.def("zone_events",
+        [](uintptr_t rows, uintptr_t out, uintptr_t state, uintptr_t pred, uintptr_t stream_of,
+           uintptr_t last, int B, int streams, int K, int R, int E, uintptr_t stream) {
+          ZoneEventsParams p;
+          p.rows = P<const uint32_t>(rows); p.out = P<uint32_t>(out); p.state = P<uint32_t>(state);
+          p.pred = P<const int>(pred); p.stream = P<const int>(stream_of); p.last = P<const int>(last);
+          p.B = B; p.streams = streams; p.K = K; p.R = R; p.E = E;
+          zone_events(p, S(stream));
+        },
+        py::arg("rows"), py::arg("out"), py::arg("state"), py::arg("pred"), py::arg("stream_of"),
+        py::arg("last"), py::arg("B"), py::arg("streams"), py::arg("K"), py::arg("R"), py::arg("E"),
+        py::arg("stream"));
+  m.def("zone_events_copy_used", [](uintptr_t src, uintptr_t dst, int B, int E, uintptr_t stream) {
+    zone_events_copy_used(P<const uint32_t>(src), P<uint32_t>(dst), B, E, S(stream));
+  });
+
   m.def("label_stable_state_bytes", &label_stable_state_bytes, py::arg("streams"), py::arg("crop_h"),
         py::arg("crop_w"));
   m.def("label_stable",

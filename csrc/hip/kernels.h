@@ -465,6 +465,28 @@ void zone_presence(const ZonePresenceParams& p, hipStream_t s);
 // only the 4 + U n used words are written, by a kernel on stream s.
 void zone_presence_copy_used(const uint32_t* src, uint32_t* dst, int B, int K, int U, hipStream_t s);
 
+// ---- zone events (zone_events.hip; the definition is postprocess/events.py) -------------------
+// After zone_presence with tracking on the same stream, with its B, K and R: out[f] = uint32[4 +
+// 4 E] = n_events, N, crop_w, crop_h, then the first min(n_events, E) events of frame f (LEAVEs,
+// then ENTERs) of four words each. `rows`: the presence rows [B, 4 + (2 + 2 R) K]; pred / stream
+// / last: the batch layout of region_tracks. `state` is carried from run to run
+// (zone_events_state_bytes: per stream the presence row of its last frame; all zero: no
+// predecessor). Every word of out is written by every run.
+struct ZoneEventsParams {
+  const uint32_t* rows = nullptr;
+  uint32_t* out = nullptr;
+  uint32_t* state = nullptr;
+  const int* pred = nullptr;
+  const int* stream = nullptr;
+  const int* last = nullptr;
+  int B = 0, streams = 0, K = 0, R = 0, E = 0;
+};
+size_t zone_events_state_bytes(int streams, int K, int R);
+void zone_events(const ZoneEventsParams& p, hipStream_t s);
+// src [B, 4 + 4 E] (zone_events' out) -> dst, the same layout in pinned host memory: per frame
+// only the 4 + 4 min(n_events, E) used words are written, by a kernel on stream s.
+void zone_events_copy_used(const uint32_t* src, uint32_t* dst, int B, int E, hipStream_t s);
+
 // ---- temporal label stabilisation (label_stable.hip; the definition is postprocess/stable.py) --
 // Ahead of every other post-processing kernel on the same stream: per stream and crop pixel a
 // label is held until a different one has been seen for `frames` (2 .. 255) consecutive frames;

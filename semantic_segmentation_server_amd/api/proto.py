@@ -255,6 +255,38 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _field(m, "has_tracks", 9, F.TYPE_BOOL)   # the regions carry track_id, age and dwell
     _field(m, "min_share", 10, F.TYPE_FLOAT)  # q / 1024 of --presence_min_share
 
+    m = fd.message_type.add(); m.name = "EventRequest"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "after_seq", 2, F.TYPE_UINT64)
+    _field(m, "max_events", 3, F.TYPE_INT32)   # 0 -> 1024
+    _field(m, "zones", 4, F.TYPE_INT32, F.LABEL_REPEATED)  # zone indices to return; empty -> all, 0 = "frame"
+
+    # one edge of a track's dwell in a zone (postprocess/events.py)
+    m = fd.message_type.add(); m.name = "ZoneEvent"
+    _field(m, "seq", 1, F.TYPE_UINT64)
+    _field(m, "epoch", 2, F.TYPE_UINT32)
+    _field(m, "kind", 3, F.TYPE_INT32)         # 1 ENTER, 2 LEAVE
+    _field(m, "frame_id", 4, F.TYPE_INT64)
+    _field(m, "timestamp", 5, F.TYPE_DOUBLE)
+    _field(m, "zone", 6, F.TYPE_INT32)
+    _field(m, "zone_name", 7, F.TYPE_STRING)
+    _field(m, "track_id", 8, F.TYPE_UINT32)
+    _field(m, "class_id", 9, F.TYPE_INT32)
+    _field(m, "label", 10, F.TYPE_STRING)
+    _field(m, "root", 11, F.TYPE_UINT32)
+    _field(m, "track_edge", 12, F.TYPE_BOOL)
+    _field(m, "pixels", 13, F.TYPE_UINT32)     # ENTER: region pixels inside the zone
+    _field(m, "dwell", 14, F.TYPE_UINT32)      # LEAVE: frames it stayed
+
+    # a stretch of the stream's event log
+    m = fd.message_type.add(); m.name = "ZoneEvents"
+    _field(m, "stream_id", 1, F.TYPE_INT32)
+    _field(m, "events", 2, F.TYPE_MESSAGE, F.LABEL_REPEATED, P + "ZoneEvent")
+    _field(m, "next_seq", 3, F.TYPE_UINT64)    # pass as after_seq next time
+    _field(m, "lost", 4, F.TYPE_UINT64)
+    _field(m, "truncated", 5, F.TYPE_UINT64)
+    _field(m, "min_share", 6, F.TYPE_FLOAT)
+
     svc = fd.service.add()
     svc.name = "SemanticSegmentationV2"
     E = ".sem_seg_server.Empty"
@@ -266,6 +298,7 @@ def v2_file_descriptor() -> descriptor_pb2.FileDescriptorProto:
     _method(svc, "GetClassRegions", P + "RegionRequest", P + "ClassRegions")
     _method(svc, "GetZoneOccupancy", P + "ZoneRequest", P + "ZoneOccupancy")
     _method(svc, "GetZonePresence", P + "PresenceRequest", P + "ZonePresence")
+    _method(svc, "GetZoneEvents", P + "EventRequest", P + "ZoneEvents")
     return fd
 
 
@@ -333,6 +366,9 @@ PresenceRequest = _cls("sem_seg_server.v2.PresenceRequest")
 ZoneHit = _cls("sem_seg_server.v2.ZoneHit")
 RegionPresence = _cls("sem_seg_server.v2.RegionPresence")
 ZonePresence = _cls("sem_seg_server.v2.ZonePresence")
+EventRequest = _cls("sem_seg_server.v2.EventRequest")
+ZoneEvent = _cls("sem_seg_server.v2.ZoneEvent")
+ZoneEvents = _cls("sem_seg_server.v2.ZoneEvents")
 
 # ---- grpc.health.v1 ---------------------------------------------------------
 HealthCheckRequest = _cls("grpc.health.v1.HealthCheckRequest")
@@ -351,6 +387,7 @@ V2_METHODS = {
     "GetClassRegions": (RegionRequest, ClassRegions),
     "GetZoneOccupancy": (ZoneRequest, ZoneOccupancy),
     "GetZonePresence": (PresenceRequest, ZonePresence),
+    "GetZoneEvents": (EventRequest, ZoneEvents),
 }
 
 

@@ -62,6 +62,7 @@ class SemanticSegmentationServicer:
 
 
 MAX_V2_OBJECTS = 4096  # per-request cap of GetStreamSegmentedObjects (padding included)
+MAX_V2_EVENTS = 1024   # GetZoneEvents' max_events when the request leaves it 0
 
 
 class SemanticSegmentationV2Servicer:
@@ -75,8 +76,10 @@ class SemanticSegmentationV2Servicer:
                  health_fn: Optional[Callable[[], Tuple[bool, int, int, str]]] = None, *,
                  serve_masks: bool = False, model_size: Tuple[int, int] = (0, 0),
                  serve_regions: bool = False, zone_names: Optional[list] = None,
-                 presence_q: int = 0):
+                 presence_q: int = 0, serve_events: bool = False):
         self.hub = hub
+        # --serve_events: GetZoneEvents is enabled (the rows are those of zone_names)
+        self.serve_events = bool(serve_events)
         # --serve_presence: q of --presence_min_share (0: GetZonePresence is off); the rows are
         # those of zone_names, and every stored item says whether it carries tracks
         self.presence_q = int(presence_q)
@@ -249,6 +252,42 @@ class SemanticSegmentationV2Servicer:
             stream_id=stream, frame_id=z.frame_id, timestamp=z.ts, width=pr.crop_w, height=pr.crop_h,
             model_width=int(self.model_size[0]), model_height=int(self.model_size[1]), regions=out,
             has_tracks=tr, min_share=self.presence_q / PR.Q_ONE)
+
+    def GetZoneEvents(self, request, context):
+        """A stretch of the stream's event log after the cursor ``after_seq``: a log, so an empty
+        answer with ``next_seq == after_seq`` is ordinary. The ``zones`` filter applies after the
+        cursor: the sequence numbers of an answer may have gaps."""
+        from ..postprocess import events as EV
+        from ..postprocess import presence as PR
+        stream = int(request.stream_id)
+        if not self.serve_events or self.zone_names is None:
+            context.set_code(grpc.StatusCode.FAILED_PRECONDITION)
+            context.set_details("zone events are not enabled (start the server with --serve_events)")
+            return P.ZoneEvents()
+        if self.hub.get(stream) is None:
+            context.set_code(grpc.StatusCode.NOT_FOUND)
+            context.set_details(f"unknown stream_id {request.stream_id}")
+            return P.ZoneEvents()
+        limit = max(1, min(int(request.max_events) or MAX_V2_EVENTS, self.hub.event_log))
+        rows, next_seq, lost = self.hub.events_after(stream, int(request.after_seq), limit)
+        if len(request.zones):
+            ev = EV.decode(np.stack([rows["w0"], rows["w1"], rows["w2"], rows["w3"]], 1))
+            rows = rows[np.isin(ev["zone"], np.array(list(request.zones), np.int64))]
+        ev = EV.decode(np.stack([rows["w0"], rows["w1"], rows["w2"], rows["w3"]], 1))
+        nz = len(self.zone_names)
+        out = []
+        for r, e in zip(rows, ev):
+            z, enter = int(e["zone"]), int(e["kind"]) == EV.ENTER
+            out.append(P.ZoneEvent(
+                seq=int(r["seq"]), epoch=int(r["epoch"]), kind=int(e["kind"]), frame_id=int(r["frame_id"]),
+                timestamp=float(r["ts"]), zone=z, zone_name=self.zone_names[z] if z < nz else "",
+                track_id=int(e["track_id"]), class_id=int(e["label"]),
+                label=label_name(self.labels, int(e["label"])), root=int(e["root"]),
+                track_edge=bool(e["edge"]), pixels=int(e["value"]) if enter else 0,
+                dwell=0 if enter else int(e["value"])))
+        return P.ZoneEvents(stream_id=stream, events=out, next_seq=next_seq, lost=lost,
+                            truncated=self.hub.events_truncated(stream),
+                            min_share=self.presence_q / PR.Q_ONE)
 
     def ListStreams(self, request, context):
         return P.StreamList(streams=[P.StreamInfo(**s) for s in self.streams])

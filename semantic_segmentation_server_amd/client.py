@@ -150,6 +150,43 @@ def print_presence(m) -> None:
                   ("  dwell {:>5}".format(h.dwell) if m.has_tracks else ""))
 
 
+def fetch_events(target: str, stream: int = 0, after_seq: int = 0, max_events: int = 0, zones=()):
+    """The ZoneEvents message of the stream's log after ``after_seq`` (v2 GetZoneEvents)."""
+    with grpc.insecure_channel(target) as ch:
+        return SemanticSegmentationV2Stub(ch).GetZoneEvents(
+            P.EventRequest(stream_id=stream, after_seq=after_seq, max_events=max_events, zones=list(zones)))
+
+
+def print_events(m) -> None:
+    """One line per event."""
+    if m.lost:
+        print("stream {}: {} events lost (they fell out of the log before this poll)".format(m.stream_id, m.lost))
+    for e in m.events:
+        print("stream {} seq {:>8} epoch {:>2} frame {:>8} ts {:.3f}  {} zone {:>2} {:<16} track {:>5}  "
+              "{:>3} {:<20} root {:>8}  {}{}".format(
+                  m.stream_id, e.seq, e.epoch, e.frame_id, e.timestamp,
+                  "ENTER" if e.kind == 1 else "LEAVE", e.zone, e.zone_name, e.track_id, e.class_id,
+                  e.label, e.root,
+                  "{:>8} px".format(e.pixels) if e.kind == 1 else "after {:>5} frames".format(e.dwell),
+                  ("  (track begins)" if e.kind == 1 else "  (track ends)") if e.track_edge else ""))
+
+
+def follow_events(target: str, stream: int = 0, follow: bool = False, period_s: float = 0.2,
+                  polls: int = None) -> int:
+    """Print the stream's log from its oldest kept event; with ``follow`` keep polling with the
+    cursor (``polls``: stop after that many polls)."""
+    seq, n = 0, 0
+    while True:
+        m = fetch_events(target, stream, seq)
+        print_events(m)
+        more = m.next_seq != seq
+        seq, n = m.next_seq, n + 1
+        if (not follow and not more) or (polls is not None and n >= polls):
+            return 0
+        if not more:
+            time.sleep(period_s)
+
+
 def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="sem_seg_server example client")
     p.add_argument("--target", default="localhost:50051")
@@ -171,7 +208,18 @@ def main(argv=None) -> int:
     p.add_argument("--presence", nargs="?", type=int, const=0, default=None, metavar="STREAM",
                    help="fetch the zone presence of the stream's latest frame (server run with "
                         "--serve_presence) and print one line per region and zone hit")
+    p.add_argument("--events", nargs="?", type=int, const=0, default=None, metavar="STREAM",
+                   help="print the stream's zone events, one line each (server run with --serve_events)")
+    p.add_argument("--follow", action="store_true",
+                   help="with --events: keep polling with the cursor and print events as they come")
     a = p.parse_args(argv)
+    if a.events is not None:
+        try:
+            return follow_events(a.target, a.events, a.follow)
+        except grpc.RpcError as err:
+            print(err.details())
+            print("{}, {}".format(err.code().name, err.code().value))
+            return 1
     if a.presence is not None:
         try:
             m = fetch_presence(a.target, a.presence)

@@ -74,6 +74,9 @@ class Config:
     zones: Optional[str] = None            # zone file (JSON, postprocess/zones.py); None: the frame zone alone
     serve_presence: bool = False           # region x zone pixel overlap, per-track dwell (v2 GetZonePresence)
     presence_min_share: float = 0.5        # share of a region's pixels inside a zone that puts it inside, in (0, 1]
+    serve_events: bool = False             # enter / leave events of the tracks per zone, every frame (v2 GetZoneEvents)
+    max_events: int = 64                   # events stored per frame (1 .. 4096); the true count is always reported
+    event_log: int = 4096                  # events kept per stream for GetZoneEvents (at least max_events)
     stable_labels: int = 0                 # hold each pixel's label until another is seen N frames in a row (0: off; 2 .. 255)
     stable_min_confidence: float = 0.0     # ignore observations below this confidence, in [0, 1] (0: no gate)
     # --- distributed ---
@@ -114,6 +117,15 @@ class Config:
                              "the overlap of the class regions with the zones (v2 GetZonePresence)")
         if self.serve_presence and not 0.0 < float(self.presence_min_share) <= 1.0:
             raise ValueError(f"--presence_min_share {self.presence_min_share} outside (0, 1]")
+        if self.serve_events:
+            if not (self.serve_presence and self.track_regions):
+                raise ValueError("--serve_events requires --serve_presence and --track_regions: an event "
+                                 "is an edge of a track's dwell in a zone (v2 GetZoneEvents)")
+            from .postprocess import events as EV
+            EV.check_geometry(int(self.max_events))
+            if int(self.event_log) < int(self.max_events):
+                raise ValueError(f"--event_log {self.event_log} is smaller than --max_events "
+                                 f"{self.max_events}: the log holds at least one frame's events")
         if int(self.stable_labels) != 0 and not 2 <= int(self.stable_labels) <= 255:
             raise ValueError(f"--stable_labels {self.stable_labels} outside 2 .. 255 (0: off)")
         if not 0.0 <= float(self.stable_min_confidence) <= 1.0:
@@ -239,6 +251,16 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--presence_min_share", type=float, default=d.presence_min_share,
                    help="share of a region's pixels inside a zone from which the region counts as "
                         "inside it (0 < share <= 1)")
+    p.add_argument("--serve_events", action="store_true",
+                   help="detect on the device, for every processed frame, the tracks that entered or "
+                        "left a zone (and were born or ended) and serve them as a log per stream (v2 "
+                        "GetZoneEvents); requires --serve_presence and --track_regions")
+    p.add_argument("--max_events", type=int, default=d.max_events, metavar="E",
+                   help="with --serve_events: events stored per frame (1 .. 4096); a frame with more "
+                        "is truncated and the true count reported")
+    p.add_argument("--event_log", type=int, default=d.event_log, metavar="N",
+                   help="with --serve_events: events kept per stream for GetZoneEvents (at least "
+                        "--max_events)")
     p.add_argument("--stable_labels", type=int, default=d.stable_labels, metavar="N",
                    help="hold each pixel's label until a different label has been seen for N "
                         "consecutive frames of its stream (2 .. 255), on the device ahead of all "

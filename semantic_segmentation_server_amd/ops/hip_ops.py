@@ -1565,6 +1565,71 @@ def zone_presence_copy_to_host(src: torch.Tensor, dst: torch.Tensor, K: int, U: 
     return dst
 
 
+def zone_events_state_bytes(streams, K, R) -> int:
+    return int(_hip_mod().zone_events_state_bytes(int(streams), int(K), int(R)))
+
+
+def zone_events(presence_rows, out, state, tables, *, counts, K, R, E):
+    """Zone events of the presence rows that ``zone_presence`` (with tracking) just wrote on the
+    current stream (csrc/hip/zone_events.hip; the format is postprocess/events.py's): per frame
+    ``out[f] = [n_events, N, crop_w, crop_h, events]``, four words an event, LEAVEs before ENTERs.
+    ``presence_rows``: uint32/int32 [B, 4 + (2 + 2 R) K]; ``out``: uint32/int32 [B, 4 + 4 E];
+    ``state``: uint8, the streams' carried rows, exactly ``zone_events_state_bytes(len(counts), K,
+    R)`` bytes (zero: no predecessor); ``tables`` / ``counts`` as for ``region_tracks``. Every word
+    of ``out`` is written."""
+    from ..postprocess import events as EV
+    from ..postprocess import presence as PR
+    K, R, E = int(K), int(R), int(E)
+    if not 1 <= K <= REGION_MAX_K or PR.MAX_REGIONS != REGION_MAX_K:
+        raise ValueError(f"zone_events: K {K} outside 1 .. {REGION_MAX_K}")
+    if not 1 <= R <= 1 + PR.MAX_ZONES:
+        raise ValueError(f"zone_events: R {R} outside 1 .. {1 + PR.MAX_ZONES}")
+    if not 1 <= E <= EV.MAX_EVENTS:
+        raise ValueError(f"zone_events: E {E} outside 1 .. {EV.MAX_EVENTS}")
+    counts = [int(c) for c in counts]
+    B = sum(counts)
+    if not counts or min(counts) < 0 or B < 1 or B > 65535 or len(counts) > 65535:
+        raise ValueError(f"zone_events: bad layout {counts}")
+    S = len(counts)
+    for t, name, width in ((presence_rows, "presence_rows", PR.frame_words(K, R, True)),
+                           (out, "out", EV.frame_words(E))):
+        if t.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"{name}: expected uint32 or int32, got {t.dtype}")
+        _chk(t, t.dtype, name)
+        if tuple(t.shape) != (B, width):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {width})")
+    if presence_rows.data_ptr() == out.data_ptr():
+        raise ValueError("zone_events: presence_rows and out are the same buffer")
+    _chk(state, torch.uint8, "state")
+    if state.numel() != zone_events_state_bytes(S, K, R):
+        raise ValueError(f"state: {state.numel()} bytes != {zone_events_state_bytes(S, K, R)}")
+    _chk(tables, torch.int32, "tables")
+    if tables.numel() != 2 * B + S:
+        raise ValueError(f"tables: {tables.numel()} words != 2 * {B} + {S}")
+    for t in (out, state, tables):
+        if t.device != presence_rows.device:
+            raise ValueError("zone_events: the buffers are on different devices")
+    p = _ptr(tables)
+    _hip_mod().zone_events(_ptr(presence_rows), _ptr(out), _ptr(state), p, p + 4 * B, p + 8 * B, B, S,
+                           K, R, E, _stream())
+    _dbg('zone_events')
+    return out
+
+
+def zone_events_copy_to_host(src: torch.Tensor, dst: torch.Tensor, E: int) -> torch.Tensor:
+    """``zone_events``' out [B, 4 + 4 E] -> dst, the same layout in PINNED host memory: per frame
+    only the header and the stored events, by a kernel on the current stream."""
+    if not src.is_cuda or dst.is_cuda or not dst.is_pinned():
+        raise ValueError("zone_events_copy_to_host: CUDA source, pinned host destination")
+    if not (src.is_contiguous() and dst.is_contiguous()) or src.element_size() != 4 or dst.element_size() != 4:
+        raise ValueError("zone_events_copy_to_host: contiguous tensors of 4-byte words required")
+    if src.dim() != 2 or tuple(src.shape) != tuple(dst.shape) or src.shape[1] != 4 + 4 * int(E):
+        raise ValueError(f"zone_events_copy_to_host: shapes {tuple(src.shape)}, {tuple(dst.shape)} != "
+                         f"[B, 4 + 4 * {E}]")
+    _hip_mod().zone_events_copy_used(src.data_ptr(), dst.data_ptr(), src.shape[0], int(E), _stream())
+    return dst
+
+
 def label_stable_state_bytes(streams, crop_h, crop_w) -> int:
     return int(_hip_mod().label_stable_state_bytes(int(streams), int(crop_h), int(crop_w)))
 

@@ -228,6 +228,10 @@ class DataParallelPipeline:
         self.presence_rows = int(getattr(engine, "presence_rows", 0) or 0)
         self.presence_unit = int(getattr(engine, "presence_unit", 0) or 0)
         self.presence_tracks = bool(getattr(engine, "presence_tracks", False))
+        # --serve_events: each step's event words ([B, 4 + 4 E]); the header and the stored events
+        # of each frame go to pinned memory by a kernel (_d2h_events), and the hub gets the rows
+        # of ALL frames of the step, in frame order: it keeps a log, not the latest frame
+        self.event_cap = int(getattr(engine, "event_cap", 0) or 0)
         # lag L >= 1: step k collects step k-L's records, with L + 1 staging slots (so L + 1
         # steps can be in flight on a slot-parallel engine); SSA_PIPE_LAG overrides a
         # non-zero lag, else the engine may ask for more depth (slot-parallel: 2)
@@ -319,6 +323,9 @@ class DataParallelPipeline:
         self.local_presence = [torch.zeros((self.B, 4 + self.presence_unit * self.region_cap), dtype=torch.int32,
                                            pin_memory=self.cuda) for _ in range(NS)] \
             if self.presence_rows else None
+        self.local_events = [torch.zeros((self.B, 4 + 4 * self.event_cap), dtype=torch.int32,
+                                         pin_memory=self.cuda) for _ in range(NS)] \
+            if self.event_cap else None
         if gather == "host" and ctx.initialized:
             self.host_send = torch.empty((self.B, self.comb_width), dtype=torch.float32)
             self.host_gather = torch.empty((ctx.world, self.B, self.comb_width), dtype=torch.float32)
@@ -551,10 +558,14 @@ class DataParallelPipeline:
                 hreg = self.engine.host_regions(labels, getattr(self.engine, "conf_plane", None),
                                                 *([strm] if self.track else []))
                 self.hub.push_regions(hreg, self._node_meta(fids, strm, tss), **self._region_kw)
-                if self.presence_rows and hasattr(self.hub, "push_presence"):
-                    self.hub.push_presence(self.engine.host_presence(labels, hreg, strm if self.track else None),
-                                           self._node_meta(fids, strm, tss), self.presence_unit,
-                                           tracks=self.presence_tracks)
+                if self.presence_rows and (hasattr(self.hub, "push_presence") or self.event_cap):
+                    hpre = self.engine.host_presence(labels, hreg, strm if self.track else None)
+                    if hasattr(self.hub, "push_presence"):
+                        self.hub.push_presence(hpre, self._node_meta(fids, strm, tss), self.presence_unit,
+                                               tracks=self.presence_tracks)
+                    if self.event_cap and hasattr(self.hub, "push_events"):
+                        self.hub.push_events(self.engine.host_events(hpre, strm),
+                                             self._node_meta(fids, strm, tss))
             if self.zone_rows and self.hub is not None and hasattr(self.hub, "push_zones"):
                 self.hub.push_zones(self.engine.host_zones(labels, getattr(self.engine, "conf_plane", None)),
                                     self._node_meta(fids, strm, tss), conf=self.zone_conf)
@@ -565,6 +576,7 @@ class DataParallelPipeline:
         regions = self.engine.region_packed if self.region_cap else None
         zones = self.engine.zone_packed if self.zone_rows else None
         presence = self.engine.presence_packed if self.presence_rows else None
+        events = self.engine.events_packed if self.event_cap else None
         slot = self._rslot
         self._rslot = (self._rslot + 1) % self.nslots
         # the packed records are produced on the engine's result stream when its
@@ -583,6 +595,8 @@ class DataParallelPipeline:
                         self._d2h(zones, self.local_zones[slot])
                     if presence is not None:
                         self._d2h_presence(presence, self.local_presence[slot])
+                    if events is not None:
+                        self._d2h_events(events, self.local_events[slot])
                 ev = self._rec_ev[slot]  # per record slot: collected before the slot is reused
                 ev.record(rs)
             else:
@@ -595,6 +609,8 @@ class DataParallelPipeline:
                     self._d2h(zones, self.local_zones[slot])
                 if presence is not None:
                     self._d2h_presence(presence, self.local_presence[slot])
+                if events is not None:
+                    self._d2h_events(events, self.local_events[slot])
                 if self.cuda:
                     ev = self._rec_ev[slot]
                     ev.record(fast_cuda.current_stream(self.dev_index))
@@ -628,6 +644,8 @@ class DataParallelPipeline:
                 self._d2h(zones, self.local_zones[slot])
             if presence is not None:
                 self._d2h_presence(presence, self.local_presence[slot])
+            if events is not None:
+                self._d2h_events(events, self.local_events[slot])
             # every rank (non-root ones too) records the step and goes through the lag
             # throttle: meta_host[slot] is rewritten only after the step that last used it
             # has been collected, i.e. after its H2D copy ran (VERDICT r3 Weak #4: non-root
@@ -682,6 +700,16 @@ class DataParallelPipeline:
                 and getattr(self.engine, "backend", "hip") == "hip":
             from ..ops import hip_ops
             hip_ops.zone_presence_copy_to_host(src, dst, self.region_cap, self.presence_unit)
+        else:
+            dst.copy_(src, non_blocking=self.cuda)
+
+    def _d2h_events(self, src: torch.Tensor, dst: torch.Tensor) -> None:
+        """Event words -> pinned host buffer on the current stream, as ``_d2h_presence``: the HIP
+        build copies only each frame's header and its stored events (a quiet frame: four words)."""
+        if self.cuda and src.is_cuda and dst.is_pinned() and src.is_contiguous() \
+                and getattr(self.engine, "backend", "hip") == "hip":
+            from ..ops import hip_ops
+            hip_ops.zone_events_copy_to_host(src, dst, self.event_cap)
         else:
             dst.copy_(src, non_blocking=self.cuda)
 
@@ -857,6 +885,8 @@ class DataParallelPipeline:
         if self.presence_rows and hasattr(self.hub, "push_presence"):
             self.hub.push_presence(self.local_presence[slot].numpy(), meta, self.presence_unit,
                                    tracks=self.presence_tracks)
+        if self.event_cap and hasattr(self.hub, "push_events"):  # every frame of the step
+            self.hub.push_events(self.local_events[slot].numpy(), meta)
 
     def _push_zones(self, slot: int, meta: np.ndarray) -> None:
         """The same for the collected step's zone words, if the hub takes zones."""

@@ -23,8 +23,19 @@ class DevicePostprocess:
                  region_classes: int = 0, region_min_pixels: int = 1, region_conf: bool = False,
                  track_streams: int = 0, track_q: int = 0, zone_rows: int = 0, zone_classes: int = 0,
                  zone_conf: bool = False, presence_rows: int = 0, presence_q: int = 0,
-                 stable_frames: int = 0, stable_gate: int = 0, stable_streams: int = 0):
+                 stable_frames: int = 0, stable_gate: int = 0, stable_streams: int = 0,
+                 event_cap: int = 0):
         self.device = device
+        # event_cap (--serve_events): E of the zone-event kernels (zone_events.hip), the events
+        # stored per frame; 0: no kernel, no buffer, no launch. They end the chain, read the
+        # presence rows of the run and the track layout, and carry per stream its last presence
+        # row beside the dwell state (reset_tracks clears it too)
+        self.event_cap = int(event_cap)
+        if self.event_cap and not (presence_rows and track_streams):
+            raise ValueError("DevicePostprocess: event_cap needs presence_rows and track_streams")
+        self._event_bufs: Dict[tuple, torch.Tensor] = {}
+        self._event_state: Dict[tuple, torch.Tensor] = {}
+        self.last_events = None
         # stable_frames (--stable_labels): N of the temporal label stabilisation
         # (label_stable.hip), the first launch of run(): in place on the label maps (and on the
         # confidence plane when one is passed), so every later kernel reads the stabilised
@@ -239,6 +250,23 @@ class DevicePostprocess:
                 dtype=torch.uint8, device=self.device)
         return self._presence_bufs[key] + (self._presence_state.get(skey),)
 
+    def event_buffers(self, B: int, crop_w: int, crop_h: int):
+        """([B, 4 + 4 event_cap] int32 event words, the streams' carried presence rows) of the
+        zone-event kernels: static and shared like ``presence_buffers``; the state belongs to the
+        crop alone. Every run writes every word."""
+        key = (B, crop_w, crop_h)
+        if key not in self._event_bufs:
+            from . import events as EV
+            EV.check_geometry(self.event_cap)
+            self._event_bufs[key] = torch.zeros((B, EV.frame_words(self.event_cap)), dtype=torch.int32,
+                                                device=self.device)
+        skey = (crop_w, crop_h)
+        if skey not in self._event_state:
+            self._event_state[skey] = torch.zeros(
+                hip_ops.zone_events_state_bytes(self.track_streams, self.region_cap, self.presence_rows),
+                dtype=torch.uint8, device=self.device)
+        return self._event_bufs[key], self._event_state[skey]
+
     def reset_tracks(self) -> None:
         """Forget every stream's carried state (ids start again at 1, dwells at 0, the next
         frame's labels pass the stabilisation unchanged), once the device is idle."""
@@ -246,14 +274,15 @@ class DevicePostprocess:
             return
         torch.cuda.synchronize(self.device)
         for st in (list(self._track_state.values()) + list(self._presence_state.values())
-                   + list(self._stable_state.values())):
+                   + list(self._event_state.values()) + list(self._stable_state.values())):
             st.zero_()
         torch.cuda.synchronize(self.device)
 
     def run(self, labels: torch.Tensor, crop_w: int, crop_h: int, min_area: float,
             out: torch.Tensor = None, mask_out: torch.Tensor = None,
             region_out: torch.Tensor = None, conf: torch.Tensor = None,
-            zone_out: torch.Tensor = None, presence_out: torch.Tensor = None) -> torch.Tensor:
+            zone_out: torch.Tensor = None, presence_out: torch.Tensor = None,
+            event_out: torch.Tensor = None) -> torch.Tensor:
         """Packed records of ``labels`` into the static buffer for this B, or into ``out``
         ([B, 1 + 5K] fp32, e.g. a row slice of a bigger batch's buffer). The workspace is
         shared per B: runs that share it must be ordered on one stream. With ``mask_cap``
@@ -270,7 +299,9 @@ class DevicePostprocess:
         ``zone_conf``, which reads ``conf`` too); ``last_zones`` is the buffer written. With
         ``presence_rows`` the zone presence of the regions follows, into ``presence_buffers(B)`` or
         ``presence_out`` ([B, 4 + U region_cap] int32 rows); ``last_presence`` is the buffer
-        written. With ``stable_frames`` the label stabilisation comes first, on the same stream
+        written. With ``event_cap`` the zone events of the frames end the chain, into
+        ``event_buffers(B)`` or ``event_out`` ([B, 4 + 4 event_cap] int32 rows); ``last_events`` is
+        the buffer written. With ``stable_frames`` the label stabilisation comes first, on the same stream
         (the graph stays a chain): ``labels`` -- and ``conf``, when passed -- are overwritten in
         place with the stabilised planes, which everything above then reads; the frames are the
         next ones of their streams, laid out by ``track_counts``."""
@@ -349,6 +380,14 @@ class DevicePostprocess:
                                   K=self.region_cap, R=self.presence_rows, plane=plane,
                                   conf=self.region_conf, **kw)
             self.last_presence = words
+        if self.event_cap:
+            ewords, estate = self.event_buffers(B, crop_w, crop_h)
+            if event_out is not None:
+                ewords = event_out
+            hip_ops.zone_events(self.last_presence, ewords, estate, tables,
+                                counts=self.track_counts(B), K=self.region_cap,
+                                R=self.presence_rows, E=self.event_cap)
+            self.last_events = ewords
         return rec
 
     def fetch(self, rec: torch.Tensor, frame_ids: Sequence[int], ts: Sequence[float],
@@ -376,3 +415,4 @@ class DevicePostprocess:
     fetch_regions = fetch_masks  # the same: a uint32 row per frame with a 4-word header
     fetch_zones = fetch_masks
     fetch_presence = fetch_masks
+    fetch_events = fetch_masks

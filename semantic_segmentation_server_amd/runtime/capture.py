@@ -6,7 +6,8 @@ DevicePostprocess: the post-processing graphs of all slots advance it in replay 
 --serve_confidence plane of ``labels``, which the post-processing graph reads, or None;
 ``zones``: --serve_zones zone words, or None; ``presence``: --serve_presence presence words,
 written by the last kernels of the post-processing chain (their dwell state lives beside the
-track state), or None). With --stable_labels the first launch of the post-processing chain
+track state), or None; ``events``: --serve_events event words, written by the kernels that then
+end the chain, or None). With --stable_labels the first launch of the post-processing chain
 rewrites ``labels`` (and ``conf``) in place with the stabilised planes, whose per-stream state
 lives there too: after the post-processing they are what the step hands out.
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
@@ -60,6 +61,7 @@ class WholeStep:
             lambda: eng._step_all(frames, bgr))
         self.zones = eng._step_zones  # --serve_zones: the zone words the graph writes, or None
         self.presence = eng._step_presence  # --serve_presence: the same
+        self.events = eng._step_events  # --serve_events: the same
 
     def replay(self) -> None:
         self.graph.replay()
@@ -97,7 +99,8 @@ class SplitStep:
             self.model, _ = _graph(infer)
         self.post_graph, (self.post, self.mask, self.regions) = _graph(lambda: eng._post_and_mask(lab, conf=cf))
         self.zones = eng.device_zones()  # --serve_zones, or None
-        self.presence = eng.device_presence()  # --serve_presence: the last kernels of the chain, or None
+        self.presence = eng.device_presence()  # --serve_presence: after the zones in the chain, or None
+        self.events = eng.device_events()  # --serve_events: the last kernels of the chain, or None
         self.rs, self.post_done = eng.result_stream, torch.cuda.Event()
 
     def replay(self) -> None:
@@ -169,6 +172,9 @@ class PartsStep:
         if eng.presence_rows:
             self.presence = pr = torch.zeros((B, 4 + eng.presence_unit * eng.region_cap), dtype=torch.int32,
                                              device=dev)
+        self.events = evs = None
+        if eng.event_cap:
+            self.events = evs = torch.zeros((B, 4 + 4 * eng.event_cap), dtype=torch.int32, device=dev)
         parts = [(lambda i=i, sl=sl: hm.segment(eng.to_bgr(frames[sl], out=bgr[sl] if bgr is not None else None),
                                                 eng.lut_x, eng.lut_y, out=lab[sl], part=i,
                                                 conf_out=cf[sl] if cf is not None else None),
@@ -177,7 +183,8 @@ class PartsStep:
                                                  region_out=reg[sl] if reg is not None else None,
                                                  conf=cf[sl] if cf is not None else None,
                                                  zone_out=zn[sl] if zn is not None else None,
-                                                 presence_out=pr[sl] if pr is not None else None))
+                                                 presence_out=pr[sl] if pr is not None else None,
+                                                 event_out=evs[sl] if evs is not None else None))
                  for i, sl in enumerate(sls)]  # per part: (model, records)
         for run in [m for m, _ in parts] + [r for _, r in parts]:  # warm-up outside capture
             run()

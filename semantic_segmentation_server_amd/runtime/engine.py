@@ -200,6 +200,23 @@ class Engine:
         self.presence_packed: Optional[torch.Tensor] = None
         self.presence: Optional[np.ndarray] = None
         self._step_presence = None  # the presence words of the step _step_all issued last
+        # --serve_events: the enter / leave edges of the presence state between consecutive frames
+        # of a stream (postprocess/events.py). event_cap: E, the events stored per frame (0 = off:
+        # no kernel, no buffer); events_packed / events: as presence_packed / presence, [B, 4 +
+        # 4 E] words. The device state (each stream's last presence row) lives in the one
+        # DevicePostprocess; the host paths keep a StreamEvents per stream id
+        self.event_cap = 0
+        self._events = None
+        if getattr(cfg, "serve_events", False):
+            if not (getattr(cfg, "serve_presence", False) and self.track_regions):
+                raise ValueError("--serve_events requires --serve_presence and --track_regions")
+            from ..postprocess import events as EV
+            self.event_cap = int(getattr(cfg, "max_events", EV.DEFAULT_MAX_EVENTS))
+            EV.check_geometry(self.event_cap)
+            self._events = EV.Events(self.event_cap)
+        self.events_packed: Optional[torch.Tensor] = None
+        self.events: Optional[np.ndarray] = None
+        self._step_events = None  # the event words of the step _step_all issued last
         # --stable_labels N: every pixel keeps its label until another has been seen for N
         # consecutive frames of its stream (postprocess/stable.py), ahead of all post-processing:
         # the label maps (and the confidence plane) of a step ARE the stabilised ones. On the
@@ -337,22 +354,25 @@ class Engine:
                      region_out: Optional[torch.Tensor] = None,
                      conf: Optional[torch.Tensor] = None,
                      zone_out: Optional[torch.Tensor] = None,
-                     presence_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     presence_out: Optional[torch.Tensor] = None,
+                     event_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         return self._post_and_mask(labels, out, mask_out, region_out, conf, zone_out,
-                                   presence_out)[0]  # the records alone
+                                   presence_out, event_out)[0]  # the records alone
 
     def _post_and_mask(self, labels: torch.Tensor, out: Optional[torch.Tensor] = None,
                        mask_out: Optional[torch.Tensor] = None,
                        region_out: Optional[torch.Tensor] = None,
                        conf: Optional[torch.Tensor] = None,
                        zone_out: Optional[torch.Tensor] = None,
-                       presence_out: Optional[torch.Tensor] = None):
+                       presence_out: Optional[torch.Tensor] = None,
+                       event_out: Optional[torch.Tensor] = None):
         """(device records of ``labels``, with ``mask_cap`` their run-length masks else None,
         with ``region_cap`` their class regions else None), each right after the other on the
         same stream: one captured graph, a chain, holds all. ``conf``: the confidence plane of
         ``labels`` (``serve_confidence``), summed per region. With ``zone_rows`` the zone
         occupancy ends the chain; its words are ``device_zones()``. With ``presence_rows`` the
-        zone presence follows it; its words are ``device_presence()``."""
+        zone presence follows it; its words are ``device_presence()``. With ``event_cap`` the zone
+        events end the chain; their words are ``device_events()``."""
         if self._hip_post is None:
             from ..postprocess.device import DevicePostprocess
             # one histogram bin per model class (argmax labels are < num_classes): the
@@ -371,12 +391,15 @@ class Engine:
                                                presence_q=self.presence_q,
                                                stable_frames=self.stable_frames,
                                                stable_gate=self.stable_gate,
-                                               stable_streams=self.stable_streams)
+                                               stable_streams=self.stable_streams,
+                                               **({"event_cap": self.event_cap} if self.event_cap else {}))
             if self.zone_rows > 1:
                 self._hip_post.set_zone_plane(self.zone_plane)
         kw = {"zone_out": zone_out} if self.zone_rows else {}
         if self.presence_rows:
             kw["presence_out"] = presence_out
+        if self.event_cap:
+            kw["event_out"] = event_out
         rec = self._hip_post.run(labels, self.crop_w, self.crop_h, self.min_area, out=out,
                                  mask_out=mask_out, region_out=region_out, conf=conf, **kw)
         return (rec, self._hip_post.last_mask if self.mask_cap else None,
@@ -390,6 +413,10 @@ class Engine:
         """The presence words the device post-processing wrote last (None without
         ``presence_rows``)."""
         return self._hip_post.last_presence if self.presence_rows and self._hip_post is not None else None
+
+    def device_events(self) -> Optional[torch.Tensor]:
+        """The event words the device post-processing wrote last (None without ``event_cap``)."""
+        return self._hip_post.last_events if self.event_cap and self._hip_post is not None else None
 
     def _use_device_post(self) -> bool:
         return self.is_cuda and self.cfg.contour_mode == "fast"
@@ -443,6 +470,8 @@ class Engine:
         self._track_ids = {}
         if self._dwells is not None:
             self._dwells.reset()
+        if self._events is not None:
+            self._events.reset()
         if self._hip_post is not None:
             self._hip_post.reset_tracks()
 
@@ -524,6 +553,21 @@ class Engine:
                       tab=tab, dwell=self._dwells.of(streams[b]) if tr else None, out=out[b])
         return out
 
+    def host_events(self, presence, streams=None) -> np.ndarray:
+        """uint32 [B, 4 + 4 E] event words of host presence words by the numpy definition
+        (postprocess/events.py): the CPU path, and a GPU without device post-processing.
+        ``presence``: the presence words of the frames (``host_presence``); the frames advance the
+        StreamEvents of their ``streams`` in row order, as the dwell state there."""
+        from ..postprocess import events as EV
+        from ..postprocess import presence as PR
+        pr = presence.cpu().numpy() if isinstance(presence, torch.Tensor) else np.asarray(presence)
+        pr = pr.view(np.uint32)
+        streams = self.track_layout(pr.shape[0]) if streams is None else _per_frame(streams, pr.shape[0])
+        out = np.zeros((pr.shape[0], EV.frame_words(self.event_cap)), np.uint32)
+        for b in range(pr.shape[0]):
+            self._events.of(streams[b]).update(PR.decode(pr[b], self.presence_rows, tracks=True), out=out[b])
+        return out
+
     def _step_outputs(self, frames: torch.Tensor, bgr: Optional[torch.Tensor] = None):
         """One eager step: (labels, packed records or None, mask run words or None, region
         words or None)."""
@@ -536,6 +580,7 @@ class Engine:
             out = (labels, *self._post_and_mask(labels, conf=conf), conf)
             self._step_zones = self.device_zones()
             self._step_presence = self.device_presence()
+            self._step_events = self.device_events()
             return out
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
@@ -549,6 +594,8 @@ class Engine:
             if host and self.zone_rows else None
         self._step_presence = torch.from_numpy(self.host_presence(labels, regions).view(np.int32)) \
             if host and self.presence_rows else None
+        self._step_events = torch.from_numpy(self.host_events(self._step_presence).view(np.int32)) \
+            if host and self.event_cap else None
         post = self._host_packed(labels) if host and self.cfg.contour_mode != "none" else None
         return labels, post, mask, regions, conf
 
@@ -556,6 +603,7 @@ class Engine:
         labels, post, self.mask_packed, self.region_packed, self.conf_plane = self._step_all(frames)
         self.zone_packed = self._step_zones
         self.presence_packed = self._step_presence
+        self.events_packed = self._step_events
         return labels, post
 
     def _host_packed(self, labels: torch.Tensor) -> torch.Tensor:
@@ -697,6 +745,7 @@ class Engine:
         self.conf_plane = step.conf
         self.zone_packed = step.zones
         self.presence_packed = step.presence
+        self.events_packed = getattr(step, "events", None)
         return self._gpu_host_stable(step.labels), step.post
 
     def _gpu_host_stable(self, labels: torch.Tensor) -> torch.Tensor:
@@ -770,6 +819,8 @@ class Engine:
                 self.zones = self.host_zones(labels, self.conf_plane)
             if self.presence_rows:
                 self.presence = self.host_presence(labels, self.regions, streams)
+            if self.event_cap:
+                self.events = self.host_events(self.presence, streams)
             return self.records_from_labels(labels, frame_ids, ts, streams)
         tr = self.tracer
         if self._use_device_post():
@@ -792,6 +843,8 @@ class Engine:
                     self.zones = self._hip_post.fetch_zones(self.zone_packed)
                 if self.presence_rows:
                     self.presence = self._hip_post.fetch_presence(self.presence_packed)
+                if self.event_cap:
+                    self.events = self._hip_post.fetch_events(self.events_packed)
             else:
                 recs = None
         self.stream.synchronize()
@@ -803,6 +856,8 @@ class Engine:
             self.zones = self.host_zones(labels, self.conf_plane)
         if self.presence_rows and post is None:
             self.presence = self.host_presence(labels, self.regions, streams)
+        if self.event_cap and post is None:
+            self.events = self.host_events(self.presence, streams)
         if self.debug is not None and self.debug.want():
             self.debug.dump(self._host_bgr(frames_host[0]), labels[0].cpu().numpy(), self.crop_w, self.crop_h,
                             _per_frame(streams, len(frame_ids))[0], int(frame_ids[0]))

@@ -163,6 +163,9 @@ class Producer(threading.Thread):
                         self.hub.push_presence(presence, np.array([ids, streams, ts], np.float64).T,
                                                self.engine.presence_unit,
                                                tracks=bool(self.engine.presence_tracks))
+                    events = getattr(self.engine, "events", None)
+                    if events is not None and hasattr(self.hub, "push_events"):  # --serve_events
+                        self.hub.push_events(events, np.array([ids, streams, ts], np.float64).T)
                 self.metrics.observe("objects_per_frame", len(recs) / max(1, len(ids)))
                 self.metrics.observe("buffer_depth", self.hub.depth)
                 dt = (time.perf_counter() - t0) * 1e3

@@ -40,6 +40,94 @@ RECORD_DTYPE = np.dtype([
 ])
 
 
+# One zone event of the log (--serve_events): ``seq`` counts a stream's events from 1, ``epoch``
+# its worker incarnations (track ids are unique only within one), w0 .. w3 are the event's words
+# (postprocess/events.py). A row whose ``w0`` is 0 is no event: it carries in ``w1`` the number of
+# events a frame could not store (the supervisor's channel; never kept in the log).
+EVENT_DTYPE = np.dtype([
+    ("seq", np.uint64),
+    ("epoch", np.uint32),
+    ("stream", np.int32),
+    ("frame_id", np.int64),
+    ("ts", np.float64),
+    ("w0", np.uint32),
+    ("w1", np.uint32),
+    ("w2", np.uint32),
+    ("w3", np.uint32),
+])
+DEFAULT_EVENT_LOG = 4096
+
+
+def event_rows(rows: np.ndarray, meta: np.ndarray, hot: Optional[np.ndarray] = None) -> np.ndarray:
+    """EVENT_DTYPE rows (``seq`` and ``epoch`` 0) of the frames ``hot`` (default: those with a
+    non-zero count) of a batch of [F, 4 + 4 E] event words, in frame order; a truncated frame is
+    followed by a ``w0 == 0`` row with the number of events it did not store."""
+    rows = np.asarray(rows)
+    if rows.dtype != np.uint32:
+        rows = rows.view(np.uint32)
+    E = (rows.shape[1] - 4) // 4
+    if hot is None:
+        hot = np.flatnonzero(rows[:, 0])
+    hot = np.asarray(hot, np.int64)
+    if hot.size == 0:
+        return np.zeros(0, EVENT_DTYPE)
+    # vectorised over the hot frames: frame f contributes k[f] events and, if truncated, a count row
+    n = rows[hot, 0].astype(np.int64)
+    k = np.minimum(n, E)
+    cnt = k + (n > k)
+    frame = np.repeat(np.arange(len(hot)), cnt)
+    j = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)   # position within its frame
+    is_ev = j < k[frame]
+    m = np.asarray(meta, np.float64)[hot]
+    ev = np.zeros(len(frame), EVENT_DTYPE)
+    ev["frame_id"], ev["stream"], ev["ts"] = m[frame, 0], m[frame, 1], m[frame, 2]
+    w = rows[hot, 4:4 + 4 * E].reshape(len(hot), E, 4)[frame[is_ev], j[is_ev]]
+    for c, name in enumerate(("w0", "w1", "w2", "w3")):
+        ev[name][is_ev] = w[:, c]
+    ev["w1"][~is_ev] = (n - k)[frame[~is_ev]]
+    return ev
+
+
+class _EventLog:
+    """A stream's ring of its last ``cap`` events."""
+
+    def __init__(self, cap: int):
+        self.ring = np.zeros(int(cap), EVENT_DTYPE)
+        self.seq = 0        # of the newest event; the ring holds seq - cap + 1 .. seq
+        self.epoch = 0
+        self.truncated = 0
+
+    def append(self, ev: np.ndarray) -> None:
+        """``ev``: EVENT_DTYPE rows of this stream, in order; their seq and epoch are set here."""
+        marks = ev["w0"] == 0
+        if marks.any():
+            self.truncated += int(ev["w1"][marks].sum())
+            ev = ev[~marks]
+        n, cap = len(ev), len(self.ring)
+        if n == 0:
+            return
+        ev = np.array(ev, copy=True)
+        ev["seq"] = np.arange(self.seq + 1, self.seq + n + 1, dtype=np.uint64)
+        ev["epoch"] = self.epoch
+        self.seq += n
+        ev = ev[-cap:]
+        s = (self.seq - len(ev)) % cap        # the slot of ev[0]: two slice copies at a wrap
+        head = min(len(ev), cap - s)
+        self.ring[s:s + head] = ev[:head]
+        self.ring[:len(ev) - head] = ev[head:]
+
+    def after(self, after_seq: int, limit: int):
+        cap, last = len(self.ring), self.seq
+        after_seq = min(max(0, int(after_seq)), last)  # a cursor from another server's life: its end
+        lo = max(after_seq + 1, last - cap + 1)
+        hi = min(last, lo + max(0, int(limit)) - 1)
+        lost = lo - (after_seq + 1)
+        if hi < lo:
+            return np.zeros(0, EVENT_DTYPE), after_seq + lost, lost
+        at = (np.arange(lo, hi + 1, dtype=np.int64) - 1) % cap
+        return self.ring[at], hi, lost
+
+
 def empty_records(n: int = 0) -> np.ndarray:
     return np.zeros(n, dtype=RECORD_DTYPE)
 
@@ -184,10 +272,15 @@ class ResultHub:
     """One ``ResultBuffer`` per stream id (and, with --serve_masks, its latest mask; with
     --serve_regions, its latest class regions)."""
 
-    def __init__(self, num_streams: int = 1, maxlen: Optional[int] = 4096):
+    def __init__(self, num_streams: int = 1, maxlen: Optional[int] = 4096,
+                 event_log: int = DEFAULT_EVENT_LOG):
         self.buffers: Dict[int, ResultBuffer] = {
             s: ResultBuffer(maxlen) for s in range(num_streams)}
         self.maxlen = maxlen
+        if int(event_log) < 1:
+            raise ValueError(f"--event_log {event_log} must be at least 1")
+        self.event_log = int(event_log)
+        self._event_logs: Dict[int, _EventLog] = {}
         self._lock = threading.Lock()
         self._masks: Dict[int, StoredMask] = {}
         self._regions: Dict[int, StoredRegions] = {}
@@ -319,6 +412,66 @@ class ResultHub:
         first one."""
         with self._lock:
             return self._presence.get(int(stream))
+
+    # ---- zone events (--serve_events): a LOG per stream, every frame's events in frame order
+    def _log(self, stream: int) -> _EventLog:  # under the lock
+        log = self._event_logs.get(int(stream))
+        if log is None:
+            log = self._event_logs[int(stream)] = _EventLog(self.event_log)
+        return log
+
+    def push_events(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """``rows``: [F, 4 + 4 E] event words of a collected batch (postprocess/events.py; uint32,
+        or int32 bits), ``meta``: [F, 3] (frame id, stream, capture ts) in the same order. The
+        stored events of EVERY frame are appended to their streams' logs, in frame order, with the
+        next sequence numbers; what a frame could not store adds to the stream's ``truncated``.
+        A batch without an event returns after one vectorised test."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint32:
+            rows = rows.view(np.uint32)
+        hot = np.flatnonzero(rows[:, 0])
+        if hot.size == 0:
+            return
+        self.push_event_rows(event_rows(rows, meta, hot))
+
+    def push_event_rows(self, ev: np.ndarray) -> None:
+        """Append EVENT_DTYPE rows (any streams, in order; ``event_rows``): the hub assigns
+        ``seq`` and ``epoch``."""
+        if len(ev) == 0:
+            return
+        streams = ev["stream"]
+        one = bool((streams == streams[0]).all())
+        with self._lock:
+            if one:
+                self._log(int(streams[0])).append(ev)
+                return
+            for s in np.unique(streams):
+                self._log(int(s)).append(ev[streams == s])
+
+    def events_after(self, stream: int, after_seq: int, limit: int = 1024):
+        """(events, next_seq, lost): up to ``limit`` events of ``stream`` with ``seq >
+        after_seq`` (EVENT_DTYPE, a copy, oldest first), the cursor to pass next time, and how
+        many events past ``after_seq`` have already fallen out of the log. A cursor beyond the
+        stream's newest event (from an earlier life of the server) restarts at its end."""
+        with self._lock:
+            log = self._event_logs.get(int(stream))
+            if log is None:
+                return np.zeros(0, EVENT_DTYPE), 0, 0
+            ev, nxt, lost = log.after(after_seq, limit)
+            return np.array(ev, copy=True), int(nxt), int(lost)
+
+    def events_truncated(self, stream: int) -> int:
+        """Events of ``stream`` that its frames could not store (``--max_events``)."""
+        with self._lock:
+            log = self._event_logs.get(int(stream))
+            return log.truncated if log is not None else 0
+
+    def bump_epoch(self, streams: Iterable[int]) -> None:
+        """A new worker incarnation serves ``streams``: their later events carry the next epoch
+        (track ids are unique only within one; the LEAVEs of tracks open at a crash never come)."""
+        with self._lock:
+            for s in streams:
+                self._log(int(s)).epoch += 1
 
     @property
     def depth(self) -> int:

@@ -27,6 +27,12 @@ inside a write cannot leave a lock held or half a message behind for its success
   writes it); the parent copies the newest complete slot into its hub and keeps its
   previous copy when it meets a slot being written. Class regions (``--serve_regions``)
   travel the same way, in a channel of their own with six words per entry.
+* events (``--serve_events``): a second ``_RecordRing``, of ``EVENT_DTYPE`` rows: the worker
+  pushes the stored events of EVERY frame of a step in frame order (nothing when the step has
+  none), the parent appends them to the hub's per-stream log, which assigns the sequence
+  numbers. A restarted worker starts its tracks again at id 1, so the parent bumps the epoch
+  of its streams; the LEAVE events of the tracks that were open when a worker died are never
+  emitted (a client sees the epoch change instead).
 * progress: the ring header carries the worker's step count and the time of its last
   step, written by the worker's producer loop itself -- liveness is step PROGRESS, not a
   timer thread, so a worker whose GPU hangs (producer stuck in a synchronize) goes stale
@@ -73,7 +79,7 @@ from typing import List, Optional
 import numpy as np
 
 from ..config import Config
-from .results import RECORD_DTYPE, latest_rows
+from .results import EVENT_DTYPE, RECORD_DTYPE, event_rows, latest_rows
 
 log = logging.getLogger(__name__)
 
@@ -90,9 +96,10 @@ class _RecordRing:
 
     HDR = 8
 
-    def __init__(self, cap: int = 1 << 16, name: Optional[str] = None):
+    def __init__(self, cap: int = 1 << 16, name: Optional[str] = None, dtype=RECORD_DTYPE):
         self.cap = int(cap)
-        nbytes = self.HDR * 8 + self.cap * RECORD_DTYPE.itemsize
+        self.dtype = dtype = np.dtype(dtype)  # the rows': RECORD_DTYPE, or EVENT_DTYPE (the events ring)
+        nbytes = self.HDR * 8 + self.cap * dtype.itemsize
         self.owner = name is None
         self.shm = shared_memory.SharedMemory(name=name, create=self.owner, size=nbytes if self.owner else 0)
         buf = self.shm.buf
@@ -102,7 +109,7 @@ class _RecordRing:
             self.hdr[5] = self.cap
         else:
             self.cap = int(self.hdr[5])  # the segment may be page-rounded: cap from the header
-        self.rows = np.ndarray((self.cap,), dtype=RECORD_DTYPE, buffer=buf, offset=self.HDR * 8)
+        self.rows = np.ndarray((self.cap,), dtype=dtype, buffer=buf, offset=self.HDR * 8)
         self.ts = np.ndarray((1,), dtype=np.float64, buffer=buf, offset=4 * 8)
         if self.owner:
             self.ts[0] = time.time()
@@ -137,10 +144,10 @@ class _RecordRing:
         w, r = int(self.hdr[0]), int(self.hdr[1])
         n = w - r
         if n <= 0:
-            return np.zeros(0, dtype=RECORD_DTYPE)
+            return np.zeros(0, dtype=self.dtype)
         s = r % self.cap
         k = min(n, self.cap - s)
-        out = np.empty(n, dtype=RECORD_DTYPE)
+        out = np.empty(n, dtype=self.dtype)
         out[:k] = self.rows[s:s + k]
         if k < n:
             out[k:] = self.rows[:n - k]
@@ -283,9 +290,10 @@ class _RingHub:
 
     def __init__(self, ring: _RecordRing, masks: Optional[_WordChannel] = None,
                  regions: Optional[_WordChannel] = None, zones: Optional[_WordChannel] = None,
-                 presence: Optional[_WordChannel] = None):
+                 presence: Optional[_WordChannel] = None, events: Optional[_RecordRing] = None):
         self.ring = ring
         self.presence_ch = presence
+        self.event_ring = events
         self.masks = masks
         self.region_ch = regions
         self.zone_ch = zones
@@ -328,6 +336,21 @@ class _RingHub:
         for st, fid, ts, words in latest_rows(rows, meta, self.presence_ch.unit):
             self.presence_ch.write(st, fid, ts, words)
 
+    def push_events(self, rows: np.ndarray, meta: np.ndarray) -> None:
+        """As ResultHub.push_events, into the events ring: the stored events of EVERY frame of the
+        batch, in frame order (a truncated frame is followed by a count row); the parent's hub
+        assigns the sequence numbers. A batch without an event returns after one vectorised
+        test; events that do not fit the ring are counted as its drops."""
+        if self.event_ring is None:
+            return
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint32:
+            rows = rows.view(np.uint32)
+        hot = np.flatnonzero(rows[:, 0])
+        if hot.size == 0:
+            return
+        self.event_ring.push(event_rows(rows, meta, hot))
+
 
 def _fault_for(spec: Optional[str], rank: int, incarnation: int):
     """(kind, step) of the fault injected into this worker incarnation, or None."""
@@ -344,7 +367,7 @@ def _fault_for(spec: Optional[str], rank: int, incarnation: int):
 def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnation: int,
                  max_steps: Optional[int], mask_name: Optional[str] = None,
                  region_name: Optional[str] = None, zone_name: Optional[str] = None,
-                 presence_name: Optional[str] = None) -> None:
+                 presence_name: Optional[str] = None, event_name: Optional[str] = None) -> None:
     """Child process: rank ``rank``'s producer, reporting through the ring and ``q``."""
     logging.basicConfig(level=getattr(logging, cfg.log_level.upper(), logging.INFO),
                         format=f"%(asctime)s %(levelname)s worker{rank}: %(message)s")
@@ -361,6 +384,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
     regions = _WordChannel(name=region_name) if region_name else None
     zones = _WordChannel(name=zone_name) if zone_name else None
     presence = _WordChannel(name=presence_name) if presence_name else None
+    events = _RecordRing(name=event_name, dtype=EVENT_DTYPE) if event_name else None
     metrics = Metrics()
     device = None
     if cfg.device != "cpu" and torch.cuda.is_available() and torch.cuda.device_count() > rank:
@@ -371,7 +395,7 @@ def _worker_main(cfg: Config, rank: int, ring_name: str, q, stop_evt, incarnatio
                            cfg.source_path, fps=cfg.fps_limit, seed=cfg.seed + rank,
                            pixel_format=cfg.pixel_format)
                for s in range(S)]
-    prod = Producer(engine, sources, _RingHub(ring, masks, regions, zones, presence), metrics, cfg.batch,
+    prod = Producer(engine, sources, _RingHub(ring, masks, regions, zones, presence, events), metrics, cfg.batch,
                     max_steps=max_steps)
     fault = _fault_for(cfg.inject_fault, rank, incarnation)
 
@@ -425,6 +449,7 @@ class _Worker:
         self.regions: Optional[_WordChannel] = None
         self.zones: Optional[_WordChannel] = None
         self.presence: Optional[_WordChannel] = None
+        self.events: Optional[_RecordRing] = None
         self.q = None
         self.up = False
         self.started = 0.0
@@ -459,7 +484,8 @@ class SupervisedServer:
         self.nw = max(1, int(cfg.gpus))
         self.S = max(1, cfg.streams)
         self.metrics = Metrics()
-        self.hub = ResultHub(self.nw * self.S, cfg.buffer_max)
+        self.hub = ResultHub(self.nw * self.S, cfg.buffer_max,
+                             event_log=int(getattr(cfg, "event_log", 4096)))
         self.camera_res = probe_resolution(cfg.source, cfg.camera_idx, cfg.camera_width,
                                            cfg.camera_height, cfg.source_path,
                                            pixel_format=cfg.pixel_format)
@@ -491,7 +517,8 @@ class SupervisedServer:
                                                            serve_regions=cfg.serve_regions,
                                                            model_size=(cfg.input_size, cfg.input_size),
                                                            zone_names=self.zone_names,
-                                                           presence_q=self.presence_q),
+                                                           presence_q=self.presence_q,
+                                                           serve_events=bool(getattr(cfg, "serve_events", False))),
                           self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
         self._ctx = mp.get_context("spawn")
@@ -545,12 +572,21 @@ class SupervisedServer:
         # presence words: n entries of U words each
         w.presence = _WordChannel(self.S, int(self.cfg.max_regions), w.rank * self.S, unit=self.presence_unit) \
             if self.presence_unit else None
+        # events: a fifth channel, a ring of EVENT_DTYPE rows (every frame's events, not the
+        # latest frame's). A restarted worker starts its tracks again at id 1: its streams'
+        # events carry the next epoch, and the LEAVEs of the tracks that were open when the
+        # earlier incarnation died are never emitted
+        w.events = _RecordRing(self.ring_rows, dtype=EVENT_DTYPE) \
+            if getattr(self.cfg, "serve_events", False) else None
+        if w.events is not None and w.incarnation > 0:
+            self.hub.bump_epoch(range(w.rank * self.S, (w.rank + 1) * self.S))
         w.proc = self._ctx.Process(target=_worker_main, name=f"semseg-worker{w.rank}-{w.incarnation}",
                                    args=(self.cfg, w.rank, w.ring.name, w.q, self._stop, w.incarnation,
                                          self.max_steps, w.masks.name if w.masks is not None else None,
                                          w.regions.name if w.regions is not None else None,
                                          w.zones.name if w.zones is not None else None,
-                                         w.presence.name if w.presence is not None else None),
+                                         w.presence.name if w.presence is not None else None,
+                                         w.events.name if w.events is not None else None),
                                    daemon=True)
         w.proc.start()
         w.started = time.time()
@@ -596,6 +632,8 @@ class SupervisedServer:
         if w.presence is not None:
             for stream, fid, ts, words in w.presence.pull():
                 self.hub.put_presence(stream, fid, ts, words, tracks=bool(self.cfg.track_regions))
+        if w.events is not None:
+            self.hub.push_event_rows(w.events.pull())
         st = w.ring.steps
         if st != w.steps:
             w.steps = st
@@ -681,6 +719,12 @@ class SupervisedServer:
         if w.presence is not None:
             w.presence.close()
             w.presence = None
+        if w.events is not None:
+            dropped = w.events.drops
+            if dropped:
+                self.metrics.inc("ipc_event_drops", dropped)
+            w.events.close()
+            w.events = None
         if w.q is not None:
             try:
                 w.q.close()

@@ -41,7 +41,7 @@ class Server:
         self.cfg = cfg
         self.metrics = Metrics()
         self.labels = load_labels(cfg.labels)
-        self.hub = ResultHub(cfg.streams, cfg.buffer_max)
+        self.hub = ResultHub(cfg.streams, cfg.buffer_max, event_log=int(getattr(cfg, "event_log", 4096)))
         self.camera_res = probe_resolution(cfg.source, cfg.camera_idx, cfg.camera_width,
                                            cfg.camera_height, cfg.source_path,
                                            pixel_format=cfg.pixel_format)
@@ -66,7 +66,8 @@ class Server:
                                                    serve_regions=cfg.serve_regions,
                                                    model_size=(cfg.input_size, cfg.input_size),
                                                    zone_names=self._zone_names(),
-                                                   presence_q=int(getattr(self.engine, "presence_q", 0)))
+                                                   presence_q=int(getattr(self.engine, "presence_q", 0)),
+                                                   serve_events=bool(getattr(self.engine, "event_cap", 0)))
         S.add_v1_servicer(self.v1, self.grpc_server)
         S.add_v2_servicer(self.v2, self.grpc_server)
         S.add_health_servicer(S.HealthServicer(lambda service: self._health()[0]), self.grpc_server)
