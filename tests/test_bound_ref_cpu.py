@@ -401,6 +401,49 @@ def test_sound_aspp_pool(B, h, w, C_, N):
         BR.assert_within(F.relu(gap @ w1.t() + b1) @ w2.t(), v, e, "aspp_pool")
 
 
+def test_dw_chain_fp16_past_two_to_the_fifth():
+    """Below 2^5 the chain is exact in float64 and an exact input stays exact (e None, as
+    before); once a partial sum reaches 2^5 (BN-folded depthwise weights of the plan tests) the
+    chain carries float64's own 2^-53 relative rounding, and still contains the emulation."""
+    g = torch.Generator().manual_seed(3)
+    x = (torch.rand(2, 4, 9, 9, generator=g) * 6).half()
+    wd = (torch.rand(4, 9, generator=g) * 0.5 + 0.75).half()   # 9 taps of ~1 on values up to 6: sums to ~50
+    bd = torch.randn(4, generator=g).half()
+    for scale, big in ((1.0, True), (0.25, False)):
+        w = (wd.float() * scale).half()
+        for last in (False, True):
+            v, e = C.dw_chain_fp16((x.double(), None), w, bd, stride=1, dil=1, act=None, bias_last=last)
+            assert (float(v.abs().max()) >= 32.0) == big
+            assert (e is not None) == big
+            P = dict(Cin=4, Cout=4, stride=1, dil=1, hidP=4, we=None, residual=False, wd_h=w.t(), bd_h=bd,
+                     wp_h=torch.eye(4).half(), bp=torch.zeros(4), act="relu6", chain="bias_last" if last else None)
+            d = []
+            C.fused_ir_emulate(x, P, tile=True, hidden_hook=lambda t: d.append(t) or t)
+            vc, ec = BR.act((v, e), "relu6")
+            BR.assert_within(d[0], vc, ec, f"chain scale {scale} bias_last {last}")
+
+
+@pytest.mark.parametrize("B,H,W,C_", C.MAXPOOL)
+def test_sound_maxpool(B, H, W, C_):
+    """The max pool is exact: a correct kernel, written as the explicit maximum over the nine
+    shifted views of the -inf-padded map, equals the reference bit for bit (all-negative maps
+    included: the padding never wins); a window that misses one tap is rejected."""
+    g = torch.Generator().manual_seed(H * W)
+    x = (torch.randn(B, C_, H, W, generator=g) - 1.0).to(torch.bfloat16)
+    v, e = C.maxpool_bound(x)
+    assert e is None
+    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    assert v.shape == (B, C_, OH, OW)
+    xp = F.pad(x.float(), (1, 1, 1, 1), value=float("-inf"))
+    taps = [xp[:, :, i:i + 2 * OH - 1:2, j:j + 2 * OW - 1:2] for i in range(3) for j in range(3)]
+    BR.assert_within(torch.stack(taps).amax(0).to(torch.bfloat16), v, e, "maxpool")
+    short = torch.stack(taps[:-1]).amax(0)
+    if bool((short.double() != v).any()):
+        assert bool(BR.violations(short, v, e).any())
+    else:
+        assert H == 1  # a single row: the third row of taps is padding
+
+
 def test_sound_gap_and_its_matvec():
     """test_maxpool_gap_matvec: the fp32 mean of 31 x 29 bf16 values in two orders (pairwise
     and a running sum), and the fp32 matvec of that GAP."""

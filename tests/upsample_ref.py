@@ -26,10 +26,11 @@ def ref64(logits, K, H, W):
     return 255.0 * p, u.argmax(1), top2[:, 0] - top2[:, 1]
 
 
-def label_ref(logits, K, H, W, without=None):
-    """(float64 argmax, mask of the pixels whose top-two margin exceeds MARGIN), on the device
+def label_ref(logits, K, H, W, without=None, margin=MARGIN):
+    """(float64 argmax, mask of the pixels whose top-two margin exceeds ``margin``), on the device
     of ``logits`` (the float64 interpolant of a 2 x 1025 x 1025 x 19 map is 320 MB: the device
-    tests compute it there). ``without``: a class left out of the contest."""
+    tests compute it there). ``without``: a class left out of the contest. ``margin``: MARGIN
+    presumes |logit| <= 32; larger logits scale it (tests/plan_bound.py)."""
     u = F.interpolate(logits[..., :K].double().permute(0, 3, 1, 2), size=(H, W), mode="bilinear",
                       align_corners=True)
     if without is not None:
@@ -37,7 +38,7 @@ def label_ref(logits, K, H, W, without=None):
     if K == 1:
         return u.argmax(1), torch.ones_like(u[:, 0], dtype=torch.bool)
     top2 = u.topk(2, dim=1).values
-    return u.argmax(1), (top2[:, 0] - top2[:, 1]) > MARGIN
+    return u.argmax(1), (top2[:, 0] - top2[:, 1]) > margin
 
 
 def guarded(B, H, W):
