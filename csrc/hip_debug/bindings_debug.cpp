@@ -1,7 +1,7 @@
 // Diagnostic module _hip_debug (NOT part of the production _hip build): the LDS /
-// register poison and LDS canary kernels of debug_poison.hip, used by
-// scripts/debug_poison.py and scripts/debug_lds_canary.py. Built on demand by
-// ops/build.py build_hip_debug() (or SSA_BUILD_DEBUG=1 with build_all()).
+// register poison, its probes and the LDS canary kernels of debug_poison.hip, used by
+// tests/chip_poison.py, scripts/debug_poison.py and scripts/debug_lds_canary.py. Built by
+// ops/build.py build_all() as a module of its own.
 #include <hip/hip_runtime.h>
 #include <pybind11/pybind11.h>
 
@@ -11,6 +11,8 @@ namespace ssa {
 void poison_lds(uint32_t pat, int blocks, hipStream_t s);
 void poison_regs(int blocks, hipStream_t s);
 void lds_canary(int iters, unsigned* bad, int blocks, hipStream_t s);
+void probe_lds(uint32_t* out, uint32_t* ids, int blocks, hipStream_t s);
+void probe_regs(uint32_t* out, uint32_t* ids, int blocks, hipStream_t s);
 }  // namespace ssa
 
 PYBIND11_MODULE(_hip_debug, m) {
@@ -23,6 +25,15 @@ PYBIND11_MODULE(_hip_debug, m) {
   });
   m.def("lds_canary", [](int iters, uintptr_t bad, int blocks, uintptr_t stream) {
     ssa::lds_canary(iters, reinterpret_cast<unsigned*>(bad), blocks,
+                    reinterpret_cast<hipStream_t>(stream));
+  });
+  // out: blocks x 40960 words (LDS) / blocks x 512 words (registers); ids: blocks x 2 words
+  m.def("probe_lds", [](uintptr_t out, uintptr_t ids, int blocks, uintptr_t stream) {
+    ssa::probe_lds(reinterpret_cast<uint32_t*>(out), reinterpret_cast<uint32_t*>(ids), blocks,
+                   reinterpret_cast<hipStream_t>(stream));
+  });
+  m.def("probe_regs", [](uintptr_t out, uintptr_t ids, int blocks, uintptr_t stream) {
+    ssa::probe_regs(reinterpret_cast<uint32_t*>(out), reinterpret_cast<uint32_t*>(ids), blocks,
                     reinterpret_cast<hipStream_t>(stream));
   });
 }

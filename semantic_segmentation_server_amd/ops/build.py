@@ -6,8 +6,8 @@ Two pybind11 modules are produced next to this file:
 * ``_hip``   — HIP kernels for gfx950 (hipcc ``--offload-arch=gfx950``) plus their
   launch wrappers.
 * ``_hip_debug`` — diagnostic kernels only (csrc/hip_debug: on-chip state poison, LDS
-  canary), built on demand (``build_hip_debug``, or ``SSA_BUILD_DEBUG=1``), never part of
-  the production module. No torch C++ headers are involved: tensors cross the boundary
+  canary, the probes of tests/chip_poison.py), built by ``build_all`` as a module of its
+  own, never part of the production module. No torch C++ headers are involved: tensors cross the boundary
   as raw device pointers and the caller's HIP stream handle, so launches are
   capturable by ``torch.cuda.CUDAGraph`` (hipGraph) and compile in seconds.
 
@@ -157,10 +157,9 @@ def build_hip_debug(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_all(force: bool = False, verbose: bool = False):
-    outs = (build_host(force, verbose), build_hip(force, verbose))
-    if os.environ.get("SSA_BUILD_DEBUG", "0") == "1":
-        outs += (build_hip_debug(force, verbose),)
-    return outs
+    # the debug module always: the poisoned ids of the suite (tests/chip_poison.py) need it,
+    # and a GPU run must not depend on compiling inside a test
+    return (build_host(force, verbose), build_hip(force, verbose), build_hip_debug(force, verbose))
 
 
 if __name__ == "__main__":

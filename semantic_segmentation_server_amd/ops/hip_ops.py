@@ -1717,9 +1717,37 @@ def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> N
     state it did not write itself."""
     from .native import hip_debug
     if lds:
-        hip_debug().poison_lds(pat, 256 * 8, _stream())
+        hip_debug().poison_lds(pat, POISON_LDS_BLOCKS, _stream())
     if regs:
-        hip_debug().poison_regs(256 * 4 * 8, _stream())
+        hip_debug().poison_regs(POISON_REG_BLOCKS, _stream())
+
+
+POISON_LDS_BLOCKS = 256 * 8      # workgroups of one whole 160 KiB LDS each
+POISON_REG_BLOCKS = 256 * 4 * 8  # waves of all 512 registers each
+
+
+def probe_chip_lds(blocks: int = POISON_LDS_BLOCKS):
+    """Debug (tests/chip_poison.py): ``blocks`` workgroups each copy their whole 160 KiB LDS
+    window out without writing it. Returns (words [blocks, 40960] int32, ids [blocks, 2] int32:
+    the HW_ID and XCC_ID registers of each workgroup)."""
+    from .native import hip_debug
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.zeros(blocks, 163840 // 4, dtype=torch.int32, device=dev)
+    ids = torch.zeros(blocks, 2, dtype=torch.int32, device=dev)
+    hip_debug().probe_lds(out.data_ptr(), ids.data_ptr(), blocks, _stream())
+    return out, ids
+
+
+def probe_chip_regs(blocks: int = POISON_REG_BLOCKS):
+    """Debug: ``blocks`` waves holding the whole register file each store v96 / v160 / v224 /
+    v255 and a0 / a96 / a192 / a255, none of which they set. Returns (words [blocks, 8, 64]
+    int32, ids [blocks, 2] int32)."""
+    from .native import hip_debug
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.zeros(blocks, 8, 64, dtype=torch.int32, device=dev)
+    ids = torch.zeros(blocks, 2, dtype=torch.int32, device=dev)
+    hip_debug().probe_regs(out.data_ptr(), ids.data_ptr(), blocks, _stream())
+    return out, ids
 
 
 def copy_to_host(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:

@@ -61,7 +61,7 @@ def hip():
 
 
 def hip_debug():
-    """The diagnostic kernels (csrc/hip_debug), built on first use."""
+    """The diagnostic kernels (csrc/hip_debug): built by ``build_all``, or on first use."""
     from .build import build_hip_debug
     return _load("_hip_debug", build_hip_debug)
 

@@ -16,6 +16,8 @@ from typing import Callable, Dict, List, Optional
 import torch
 import torch.nn.functional as F
 
+import chip_poison as CP
+
 MAX_STEP = 1        # a code may be one requantisation step off ...
 MAX_SHARE = 1e-3    # ... on at most this share of a tensor's codes
 MAX_SATURATED = 1e-2
@@ -222,7 +224,7 @@ def step_reference(hm, bufs, frames, lut_x, lut_y, kind: str, spec: dict, vname:
 
 def check_plan(hm, ops, bufs, frames, lut_x, lut_y, *, run: bool = True, every_variant: bool = True,
                select: Optional[Callable[[str], bool]] = None, ref_device="cpu",
-               interior: bool = True) -> List[tuple]:
+               interior: bool = True, chip_poison: Optional[Callable] = None) -> List[tuple]:
     """Walk a ``HipDeepLabInt8`` plan in order and check every step against exact arithmetic
     on the plan's OWN input buffers as they are at that moment (teacher forcing: nothing
     accumulates from step to step).
@@ -236,7 +238,15 @@ def check_plan(hm, ops, bufs, frames, lut_x, lut_y, *, run: bool = True, every_v
     only executed. ``interior``: assert that the reference codes are not saturated (and the
     ASPP branches not dead), so a failure cannot hide behind a clamp.
 
-    Returns [(buffer, variant, share of codes off, max step)] for the int8 steps."""
+    ``chip_poison``: a reproducibility walk instead, with no reference: every variant of every
+    selected step runs three times from a sentinel-filled output, A, A' and, after
+    ``chip_poison()`` (tests/chip_poison.py: every CU's LDS and every SIMD's registers NaN), P.
+    A' != A is reported as "not reproducible", P != A with buffer, variant, the count of
+    differing elements and the first index; bit-equal, no tolerance. What A is worth is the
+    business of the walk above.
+
+    Returns [(buffer, variant, share of codes off, max step)] for the int8 steps (the poisoned
+    walk: one entry per (buffer, variant) that ran A / A' / P)."""
     from semantic_segmentation_server_amd.models.plan import Choice
 
     steps = plan_steps(hm)
@@ -291,12 +301,32 @@ def check_plan(hm, ops, bufs, frames, lut_x, lut_y, *, run: bool = True, every_v
         else:
             variants = [("op", [op])]
         refs = {}
+        if chip_poison is not None:
+            assert run, "the reproducibility walk runs the ops"
+            for vname, calls in variants:
+                snaps = []
+                for tag in ("A", "A'", "P"):
+                    out.fill_(99 if out.dtype == torch.int8 else 255 if out.dtype == torch.uint8 else float("nan"))
+                    if tag == "P":
+                        chip_poison()
+                    for c in calls:
+                        c(frames, lut_x, lut_y)
+                    if out.is_cuda:
+                        torch.cuda.synchronize()
+                    snaps.append(out if tag == "P" else out.clone())
+                for tag, b in (("not reproducible: A' != A", snaps[1]), ("the poisoned run differs: P != A", snaps[2])):
+                    d = CP.bit_diff(snaps[0], b)
+                    if d is not None:
+                        failures.append(f"{name}/{vname}: {tag} at {d[0]} of {out.numel()} elements, first at {d[1]}")
+                report.append((name, vname, 0.0, 0))
+            continue
         for vname, calls in variants:
             if calls is not None:
                 out.fill_(99 if out.dtype == torch.int8 else 255 if out.dtype == torch.uint8 else float("nan"))
                 for c in calls:
                     c(frames, lut_x, lut_y)
-                torch.cuda.synchronize()
+                if out.is_cuda:
+                    torch.cuda.synchronize()
             form = vname != "fp32" if kind == "stem" else None  # the stem reference rounds as the kernel does
             if form not in refs:
                 # compared where the buffer lives: a device-side compare costs two scalars per variant
@@ -313,17 +343,42 @@ def worst(report: List[tuple]) -> tuple:
     return max(report, key=lambda r: (r[3], r[2]))
 
 
+def reference_ops(hm, ops, bufs, frames, lut_x, lut_y, only: Optional[Callable[[str], bool]] = None) -> list:
+    """The plan's ops with every variant of every step replaced by a host function that writes
+    the step's exact reference into its buffer (as ``fill_from_references`` does): a plan that
+    ``check_plan(run=True)`` can walk on the CPU, into which a test injects a wrong op.
+    ``only(buffer name)``: the steps that write; the others leave ``bufs`` as they are."""
+    from semantic_segmentation_server_amd.models.plan import Choice
+    rd = torch.device("cpu")
+    out = []
+    for op, (kind, name, spec) in zip(ops, plan_steps(hm)):
+        def write(*args, kind=kind, name=name, spec=spec, vname="op"):
+            if only is None or only(name):
+                _write_reference(hm, bufs, frames, lut_x, lut_y, kind, name, spec, vname, rd)
+        if isinstance(op, Choice):
+            new = Choice(op.name, [(v, [lambda *a, v=v, w=write: w(vname=v)]) for v, _ in op.variants])
+            new.pick = op.pick
+            out.append(new)
+        else:
+            out.append(write)
+    return out
+
+
+def _write_reference(hm, bufs, frames, lut_x, lut_y, kind, name, spec, vname, rd):
+    ref = step_reference(hm, bufs, frames, lut_x, lut_y, kind, spec, vname, rd, interior=False)
+    out = bufs[name]
+    if kind == "logits":
+        out[..., :hm.num_classes] = ref.permute(0, 2, 3, 1).to(out.dtype)
+    elif out.dim() == 4:
+        out.copy_(ref.permute(0, 2, 3, 1).to(out.dtype))
+    else:
+        out.copy_(ref.to(out.dtype))
+
+
 def fill_from_references(hm, ops, bufs, frames, lut_x, lut_y) -> None:
     """Write into ``bufs`` what a plan whose every kernel were exact would leave there (each
     step from the buffers before it): the walker's own CPU-tier test runs on this."""
     rd = torch.device("cpu")
     for op, (kind, name, spec) in zip(ops, plan_steps(hm)):
         vname = op.variants[op.pick][0] if hasattr(op, "variants") else "op"
-        ref = step_reference(hm, bufs, frames, lut_x, lut_y, kind, spec, vname, rd, interior=False)
-        out = bufs[name]
-        if kind == "logits":
-            out[..., :hm.num_classes] = ref.permute(0, 2, 3, 1).to(out.dtype)
-        elif out.dim() == 4:
-            out.copy_(ref.permute(0, 2, 3, 1).to(out.dtype))
-        else:
-            out.copy_(ref.to(out.dtype))
+        _write_reference(hm, bufs, frames, lut_x, lut_y, kind, name, spec, vname, rd)

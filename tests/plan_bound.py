@@ -18,6 +18,15 @@ zero, the ticket buffers are all zero again and the guard bands (``SSA_GUARD_BYT
 The fp32 split-K / split-hidden partial buffers are NaN-filled too but have no reference of
 their own: how a sum is cut is the kernel's business, its total is checked in the output.
 
+``chip_poison=<callable>`` turns the walk into a reproducibility walk that needs no reference:
+every leaf call of every variant at any depth runs three times on the buffers its sub-step
+writes (outputs, fp32 partials; the ticket counters are compared too): A and A' from NaN-filled
+buffers, P from NaN-filled buffers after ``chip_poison()`` (tests/chip_poison.py: every CU's LDS
+and every SIMD's registers NaN). A != A' is "not reproducible", P != A names buffer, variant,
+the count of differing elements and the first index; the tickets and guard bands are checked
+after P. What A is worth is the business of the walks above: the same calls on the same inputs
+are held to their float64 bounds there.
+
 ``dw_chain_fp16`` is exact in float64 only below 2^5; the BN-folded depthwise operands of these
 models pass it (sum |h w| + |b| reaches 56 from the operands alone and 44 on the test frames in
 blocks 11-16), so the chain carries the 2^-53 relative term its docstring describes.
@@ -34,6 +43,7 @@ import torch
 import torch.nn.functional as F
 
 import bound_cases as BC
+import chip_poison as CP
 import upsample_ref as UR
 
 MIN_LIVE = 0.25  # least share of a clamped reference that must lie strictly inside the clamp
@@ -511,7 +521,7 @@ def label_ref(logits, K, H, W):
 # ---------------------------------------------------------------- the walker
 class Walker:
     def __init__(self, hm, ops, bufs, frames, lx, ly, *, run=True, every_variant=True, select=None, cache=None,
-                 upsample_fields=True, families=None):
+                 upsample_fields=True, families=None, chip_poison=None):
         B, Hc, Wc = (int(v) for v in frames.shape[:3])
         from semantic_segmentation_server_amd.ops import reference_ops as R
         want = R.letterbox_luts(Wc, Hc, hm.W, hm.H)[:2]  # the references letterbox as the plan's camera does
@@ -523,6 +533,8 @@ class Walker:
         self.failures: List[tuple] = []
         self.report: List[tuple] = []  # (buffer, variant, max ratio, flip share)
         self.fields, self.families = upsample_fields, families
+        self.chip_poison, self.leaves = chip_poison, 0  # leaf calls that ran A / A' / P
+        assert chip_poison is None or run, "the reproducibility walk runs the ops"
         self.dev = bufs["labels"].device
 
     # ---- inputs, references
@@ -615,8 +627,43 @@ class Walker:
             return [op.variants[op.pick]]
         return op.variants
 
+    # ---- the reproducibility walk (``chip_poison``)
+    def _tickets(self):
+        return [n for n, t in self.bufs.items() if t.dtype == torch.int32 and re.fullmatch(r"(b\d+|aspp)_cnt\d*", n)]
+
+    def _repro(self, call, names, what):
+        """A, A', P of one leaf call on the buffers ``names`` it writes (module docstring)."""
+        fill = list(names)
+        seen = []
+        for n in [n[0] if isinstance(n, tuple) else n for n in fill] + self._tickets():
+            if n in self.bufs and n not in seen:
+                seen.append(n)
+        snaps = []
+        for run in ("A", "A'", "P"):
+            self._poison(fill)
+            if run == "P":
+                self.chip_poison()
+            call(*self.args)
+            self._sync()
+            if run != "P":
+                snaps.append([self.bufs[n].clone() for n in seen])
+        self.leaves += 1
+        clean = True
+        for i, n in enumerate(seen):
+            for tag, a, b in (("not reproducible: A' != A", snaps[0][i], snaps[1][i]),
+                              ("the poisoned run differs: P != A", snaps[0][i], self.bufs[n])):
+                d = CP.bit_diff(a, b)
+                if d is not None:
+                    clean = False
+                    self.failures.append((n, what, f"{n}/{what}: {tag} at {d[0]} of {a.numel()} elements, "
+                                          f"first at {d[1]}"))
+        self.report.append((names[0][0] if isinstance(names[0], tuple) else names[0], what, 0.0, 0.0))
+        return clean
+
     def _walk_choice(self, step, op, subs_of):
         from semantic_segmentation_server_amd.models.plan import Choice
+        if self.chip_poison is not None:
+            return self._walk_choice_poisoned(step, op, subs_of)
         for vname, calls in self._variants(op):
             fam = family(op.name, vname)  # a name without a family is an error
             if self.families is not None and op.name == step.name and fam not in self.families:
@@ -642,7 +689,53 @@ class Walker:
                         self._check(sub, what)
                 self._check_state(what)
 
+    def _walk_choice_poisoned(self, step, op, subs_of):
+        from semantic_segmentation_server_amd.models.plan import Choice
+        for vname, calls in self._variants(op):
+            fam = family(op.name, vname)
+            if self.families is not None and op.name == step.name and fam not in self.families:
+                continue
+            what = vname if op.name == step.name else f"{op.name}={vname}"
+            subs = subs_of(vname)
+            assert len(subs) == len(calls), f"{op.name}/{vname}: {len(calls)} ops, {len(subs)} described"
+            for call, sub in zip(calls, subs):
+                if isinstance(call, Choice):
+                    assert call.name == sub.choice, (call.name, sub.choice)
+                    self._walk_choice_poisoned(step, call, lambda v, c=call, s=sub: nested_subs(step, c.name, s, v))
+                    continue
+                assert sub.refs, f"{op.name}/{vname}: a plain op where the nested choice {sub.choice} is expected"
+                self._repro(call, sub.writes + sub.scratch, what)
+            self._check_state(what)
+
+    def _walk_upsample_poisoned(self, step, op):
+        """Every upsample variant A / A' / P on the plan's logits and on the noise and smooth
+        fields: the label maps bit-equal."""
+        bufs = self.bufs
+        h, w = step.geom
+        B, K, ldk = bufs["logits"].shape[0], self.hm.num_classes, self.hm.ldk
+        inputs = [("plan", None)]
+        if self.fields:
+            inputs += [(f, UR.make_logits(B, h, w, K, ldk, f, seed)) for f, seed in UPSAMPLE_FIELDS]
+        saved = bufs["logits"].clone()
+        for tag, lg in inputs:
+            if lg is not None:
+                bufs["logits"].copy_(lg.to(self.dev))
+            for vname, calls in self._variants(op):
+                family("upsample", vname)
+
+                def call(*args, calls=calls):
+                    for c in calls:
+                        c(*args)
+                self._repro(call, ["labels"], f"{tag}/{vname}")
+                self._check_state(vname)
+        if len(inputs) > 1:
+            bufs["logits"].copy_(saved)
+            op(*self.args)
+            self._sync()
+
     def _walk_upsample(self, step, op):
+        if self.chip_poison is not None:
+            return self._walk_upsample_poisoned(step, op)
         hm, bufs = self.hm, self.bufs
         h, w = step.geom
         B, K, ldk = bufs["logits"].shape[0], hm.num_classes, hm.ldk
@@ -727,6 +820,9 @@ class Walker:
                 self._walk_upsample(step, op)
             elif step.choice:
                 self._walk_choice(step, op, step.subs)
+            elif self.chip_poison is not None:
+                self._repro(op, step.sub.writes + step.sub.scratch, "op")
+                self._check_state("op")
             else:
                 if self.run:
                     self._poison(step.sub.writes)
@@ -746,7 +842,8 @@ def check_plan(hm, ops, bufs, frames, lx, ly, **kw) -> List[tuple]:
     step. ``run=False``: check ``bufs`` as a finished run of the picks left them. ``select(step
     name)``: the steps to check, the others are only executed; ``families``: of their top-level
     variants, only those of these reference families (a stage split per family). ``cache``: references shared
-    between walks (reused only while a step's inputs are bit-equal). Returns [(buffer, variant,
+    between walks (reused only while a step's inputs are bit-equal). ``chip_poison``: the
+    reproducibility walk of the module docstring instead of the references. Returns [(buffer, variant,
     max |got - v| / e, flip share)]; raises ``PlanCheckError`` naming every failed check."""
     return Walker(hm, ops, bufs, frames, lx, ly, **kw).walk()
 
@@ -756,6 +853,55 @@ def worst(report):
 
 
 # ---------------------------------------------------------------- emulated plans (run=False)
+def _emulate(wk, sub, order):
+    for ref in sub.refs:
+        inp = {n: wk._input(n).detach().cpu() for n in ref.inputs}
+        for buf, sl, t in ref.emu(inp, order):
+            dst = wk.bufs[buf] if sl is None else wk.bufs[buf][..., sl]
+            dst.copy_(t.to(dst.dtype))
+
+
+def emulated_ops(hm, ops, bufs, frames, lx, ly, order: str = "whole") -> list:
+    """The plan's ops with every leaf call, of every variant at any depth, replaced by a host
+    function that writes what a correct kernel of its family leaves in the buffers (as
+    ``fill_from_emulation`` does): a plan that ``check_plan(run=True)`` can walk on the CPU, into
+    which a test injects a wrong op by replacing one callable."""
+    from semantic_segmentation_server_amd.models.plan import Choice
+    from semantic_segmentation_server_amd.ops import reference_ops as R
+    wk = Walker(hm, ops, bufs, frames, lx, ly, run=False)
+
+    def leaf(sub):
+        return lambda *args: _emulate(wk, sub, order)
+
+    def choice(step, op, subs_of):
+        variants = []
+        for vname, calls in op.variants:
+            subs = subs_of(vname)
+            assert len(subs) == len(calls), f"{op.name}/{vname}: {len(calls)} ops, {len(subs)} described"
+            variants.append((vname, [
+                choice(step, c, lambda v, c=c, s=s: nested_subs(step, c.name, s, v)) if isinstance(c, Choice) else leaf(s)
+                for c, s in zip(calls, subs)]))
+        new = Choice(op.name, variants)
+        new.pick = op.pick
+        return new
+
+    def upsample(*args):
+        lg = _nchw(bufs["logits"][..., :hm.num_classes]).float()
+        bufs["labels"].copy_(R.upsample_argmax(lg, hm.H, hm.W))
+
+    out = []
+    for op, step in zip(ops, wk.steps):
+        if step.name == "upsample":
+            new = Choice(op.name, [(vname, [upsample]) for vname, _ in op.variants])
+            new.pick = op.pick
+            out.append(new)
+        elif step.choice:
+            out.append(choice(step, op, step.subs))
+        else:
+            out.append(leaf(step.sub))
+    return out
+
+
 def fill_from_emulation(hm, ops, bufs, frames, lx, ly, order: str = "whole",
                         fault: Optional[Callable] = None, select: Optional[Callable] = None) -> None:
     """Write into ``bufs`` what a correct kernel of each PICKED family would leave there, each
@@ -769,11 +915,7 @@ def fill_from_emulation(hm, ops, bufs, frames, lx, ly, order: str = "whole",
     wk = Walker(hm, ops, bufs, frames, lx, ly, run=False)
 
     def emulate(sub):
-        for ref in sub.refs:
-            inp = {n: wk._input(n).detach().cpu() for n in ref.inputs}
-            for buf, sl, t in ref.emu(inp, order):
-                dst = bufs[buf] if sl is None else bufs[buf][..., sl]
-                dst.copy_(t.to(dst.dtype))
+        _emulate(wk, sub, order)
 
     def do_choice(step, op, subs_of):
         vname, calls = op.variants[op.pick]

@@ -48,7 +48,27 @@ seconds, one id per reference family (whole they took 6.1 s (stem), 6.2 s (block
 (block 2) and 2.3 s (block 3)): stem 3.1 s (stem_block0) and 1.7 s (separate), block 1
 1.1-1.4 s per family, block 2 3.2 s (band), 3.1 s (tile), 0.9 s (row), 0.8 s (unfused),
 block 3 0.4-0.5 s; picks-B32 3.5 s at worst (block 2), picks-B1 0.5 s.
-The whole module: 53 s.
+The whole module: 53 s without the poisoned ids below, which add 15 s.
+
+``test_bf16_plan_poisoned`` (tests/chip_poison.py; the walk mode is ``chip_poison`` of
+tests/plan_bound.py): the sweep shapes again, every leaf call of every variant at any depth three
+times on the buffers it writes -- A, A' and P, the launch of P preceded by a fill of every CU's
+LDS and every SIMD's registers with NaN -- with bit-equal outputs, fp32 partials and tickets
+required, the upsample variants' label maps on the plan's logits and on the noise and smooth
+fields included. No variant is left out and none is excused: measured on an MI355X, A = A' = P in
+every one of the
+  mnv2-129      649 leaf calls (20 ids, 0.07-0.16 s each; the first 0.65 s with the plan's build),
+  mnv2-129-rr   102 leaf calls (7 ids: the launches that take the row repeat; 0.03-0.25 s),
+  mnv2-513     1349 leaf calls (20 ids; stem and blocks 1-6 0.11-0.51 s, blocks 7-16 and ASPP,
+                the stream / lattice / split-hidden variants, 0.52-0.79 s, head and upsample
+                under 0.1 s: no id needs a split per family),
+  mobile-129    643 leaf calls (20 ids, 0.08-0.19 s),
+  resnet50-129  118 leaf calls (6 ids, 0.05-0.49 s),
+the tickets zero again and the guard bands intact after every P. No variant's summation order
+depends on arrival order (the in-launch combines sum their slabs in a fixed order): A' = A
+everywhere, so no id falls back on the float64 bound. The LDS words these kernels read as an
+index or address, and where each is written before it is read, are listed in
+tests/test_chip_poison_gpu.py.
 """
 import json
 
@@ -197,3 +217,46 @@ def test_bf16_plan(plans, shape, stage):
           f"{w[0]}/{w[1]}, largest flip share {max(r[3] for r in rep):.3e}; row repeat on in "
           f"{sum(repeat['stem_band'])} / {len(repeat['stem_band'])} stem_band and "
           f"{sum(repeat['fused_ir_slice'])} / {len(repeat['fused_ir_slice'])} slice launches")
+
+
+# ---------------------------------------------------------------- on poisoned LDS and registers
+# The sweep shapes (the picks-* plans run the same kernels); the stages whole: no reference is
+# computed, so no id needs a split per family.
+POISON_SHAPES = ("mnv2-129", "mnv2-129-rr", "mnv2-513", "mobile-129", "resnet50-129")
+POISON_PAIRS = [(s, st) for s in POISON_SHAPES for st in (
+    _RESNET if s.startswith("resnet") else _SLICED if s.endswith("-rr") else _MNV2)]
+
+
+@pytest.mark.parametrize("shape,stage", POISON_PAIRS, ids=[f"{s}-{st}" for s, st in POISON_PAIRS])
+def test_bf16_plan_poisoned(plans, shape, stage):
+    """One stage of one plan: every leaf call of every variant at any depth three times on the
+    buffers it writes -- A, A' and, with every CU's LDS and every SIMD's registers NaN-filled just
+    before the launch, P (tests/chip_poison.py): bit-equal outputs, partials and tickets, the
+    tickets zero again and the guard bands intact after P. The A outputs are those the ids of
+    ``test_bf16_plan`` hold to their float64 bounds."""
+    import chip_poison as CP
+    CP.require()
+    shape, hm, ops, bufs, (frames, lx, ly), every, cache = plans(shape)
+    assert every
+    from semantic_segmentation_server_amd.ops import fused_band as FB
+    from semantic_segmentation_server_amd.ops import hip_ops as K
+    rr = SHAPES[shape][6]
+    repeat = []  # whether each row-streaming launch got the row repeat
+    band, slice_ = K.stem_band, FB.fused_ir_slice
+    with pytest.MonkeyPatch.context() as mp:
+        _env(mp, rr)
+        mp.setattr(K, "stem_band", lambda *a, **kw: (repeat.append(bool(kw["row_repeat"])), band(*a, **kw))[1])
+        mp.setattr(FB, "fused_ir_slice", lambda *a, **kw: (repeat.append(kw.get("lut_y") is not None), slice_(*a, **kw))[1])
+        wk = PB.Walker(hm, ops, bufs, frames, lx, ly, run=True, every_variant=True, select=STAGES[stage],
+                       chip_poison=CP.poison)
+        try:
+            rep = wk.walk()
+        except AssertionError:
+            raise
+        except RuntimeError as err:  # a device fault: nothing more is launched on this GPU
+            pytest.exit(f"{shape} {stage} poisoned: {err}", returncode=3)
+    assert rep and wk.leaves == len(rep), (shape, stage, wk.leaves, len(rep))
+    if rr == "all":  # the repeat was really on, in every row-streaming launch of the stage, P included
+        assert len(repeat) >= 12 and all(repeat), repeat
+    print(f"bf16 plan {shape} {stage} poisoned: {wk.leaves} leaf calls, A = A' = P in all of them; row repeat on in "
+          f"{sum(repeat)} / {len(repeat)} row-streaming launches")

@@ -24,6 +24,13 @@ worst (buffer, variant) is r11_c1 with every LDS-DMA and streaming variant at 4.
 (register-fed v1: 8.0e-6 at worst), the stem 1.2e-6 (fp32) / 0 (MFMA forms), ASPP and
 projection 0; at 321^2 r11_out at 1.1e-5, the stem 9.0e-7 / 6.0e-7, both ASPP forms 4.4e-6.
 Each test id runs in 0.05-0.3 s after 0.5-0.8 s of setup per shape.
+
+``test_int8_plan_poisoned`` (tests/chip_poison.py, ``check_plan(chip_poison=...)``): the 129 plan
+again, every variant of every step three times from a sentinel-filled output -- A, A' and P, the
+launches of P preceded by a fill of every CU's LDS and every SIMD's registers with NaN -- and
+the outputs bit-equal. Measured on an MI355X: A = A' = P in all 692 (buffer, variant) calls (8
+stem and pool, 299 + 357 convs through every ``conv_i8`` variant, the LDS-DMA ones included, 28
+ASPP, pooling, projection, logits and labels); no variant is left out; 0.01-0.07 s per id.
 """
 import numpy as np
 import pytest
@@ -86,6 +93,28 @@ def test_int8_plan_every_variant(plan, stage):
         by_variant.setdefault(v, []).append((share, mx, name))
     print(f"int8 plan {shape} {stage}: {len(rep)} (buffer, variant) checks, worst {I.worst(rep)}; per variant "
           + ", ".join(f"{v} {max(r)[0]:.1e}" for v, r in sorted(by_variant.items())))
+
+
+@pytest.mark.parametrize("plan", ["129"], indirect=True)
+@pytest.mark.parametrize("stage", list(I.STAGES))
+def test_int8_plan_poisoned(plan, stage):
+    """One stage of the 129 plan (every tile height partial and straddling images): every variant
+    of every step three times from a sentinel-filled output -- A, A' and, with every CU's LDS and
+    every SIMD's registers NaN-filled just before the launches, P (tests/chip_poison.py): the
+    codes bit-equal, no tolerance. The A outputs are those ``test_int8_plan_every_variant``
+    holds to the exact codes."""
+    import chip_poison as CP
+    CP.require()
+    shape, hm, ops, bufs, (frames, lx, ly) = plan
+    try:
+        rep = I.check_plan(hm, ops, bufs, frames, lx, ly, run=True, every_variant=True, select=I.STAGES[stage],
+                           chip_poison=CP.poison)
+    except AssertionError:
+        raise
+    except RuntimeError as err:  # a device fault: nothing more is launched on this GPU
+        pytest.exit(f"int8 {shape} {stage} poisoned: {err}", returncode=3)
+    assert rep, stage
+    print(f"int8 plan {shape} {stage} poisoned: {len(rep)} (buffer, variant) calls, A = A' = P in all of them")
 
 
 def test_conv_i8_refuses_what_it_cannot_do():

@@ -12,6 +12,10 @@ teacher forcing permits. Negative: each injected fault is reported at exactly it
 steps after it are emulated from the damaged buffer, as a plan with one wrong kernel would run.
 Structure: ``plan_steps`` matches the ops of every bf16 key of the tune file, through every
 variant at every depth, launching nothing.
+The reproducibility walk (``chip_poison``, the mode of the poisoned device ids): on a plan of
+host ops (``emulated_ops``) a clean plan passes, an op that reads a hidden tensor the poison
+callable NaN-fills is reported as P != A, one that adds its call count as not reproducible,
+each at its buffer and variant.
 """
 import json
 import os
@@ -249,6 +253,68 @@ def test_fault_projection_residual_omitted(no_gpu):
             bufs_["b8_out"].copy_((bufs_["b8_out"].float() - bufs_["b7_out"].float()).to(torch.bfloat16))
     PB.fill_from_emulation(hm, ops, bufs, frames, lx, ly, fault=fault)
     assert _reported(hm, ops, bufs, frames, lx, ly) == {"b8_out"}
+
+
+# ---------------------------------------------------------------- the reproducibility walk
+def _poisoned_walk(wrong, steps=("block5", "block8", "upsample")):
+    """``check_plan(chip_poison=...)`` over ``steps`` of an emulated plan with host ops
+    (``plan_bound.emulated_ops``), the picks only; ``wrong(step, call, bufs, hidden, calls)``
+    wraps the last leaf call of each step's pick. The poison callable NaN-fills ``hidden``, the
+    stand-in for on-chip state. Returns (picks by step, report)."""
+    hm, ops, bufs, frames, lx, ly = _plan("mnv2", 2, 129, 160, 120)
+    _set_picks(ops, MNV2_PICKS[0])
+    PB.fill_from_emulation(hm, ops, bufs, frames, lx, ly)
+    hops = PB.emulated_ops(hm, ops, bufs, frames, lx, ly)
+    hidden, calls, picks = torch.zeros(1), [0], {}
+    for op in hops:
+        if getattr(op, "name", None) in steps:
+            vname, leaves = op.variants[op.pick]
+            picks[op.name] = vname
+            leaves[-1] = wrong(op.name, leaves[-1], bufs, hidden, calls)
+    assert set(picks) == set(steps)
+    # the unselected steps are only executed: no-ops here, their buffers are filled already
+    hops = [op if getattr(op, "name", None) in steps else type(op)(op.name, [("op", [])]) if hasattr(op, "variants")
+            else (lambda *a: None) for op in hops]
+    wk = PB.Walker(hm, hops, bufs, frames, lx, ly, run=True, every_variant=False, select=lambda n: n in steps,
+                   chip_poison=lambda: hidden.fill_(float("nan")), upsample_fields=False)
+    return picks, wk
+
+
+def test_poisoned_walk_passes_on_clean_ops(no_gpu):
+    picks, wk = _poisoned_walk(lambda step, call, bufs, hidden, calls: call)
+    rep = wk.walk()
+    # one entry per leaf call, named by the first buffer it writes (block 8's pick has two)
+    assert {("b5_out", picks["block5"]), ("b8_out", picks["block8"]), ("labels", f"plan/{picks['upsample']}")} <= \
+        {(b, v) for b, v, *_ in rep}
+    assert wk.leaves == len(rep) >= 3
+
+
+def test_poisoned_walk_sees_stale_state_and_a_call_counter(no_gpu):
+    """An op that adds a hidden host tensor (NaN once poisoned, cleared by the op as a kernel
+    overwrites its LDS) is reported as P != A at its buffer and variant; one that adds its call
+    count as not reproducible; the clean steps beside them are not reported."""
+    def wrong(step, call, bufs, hidden, calls):
+        def stale(*a):
+            call(*a)
+            t = bufs["b5_out"]
+            t[1, 2, 3, 4] = t[1, 2, 3, 4].float() + hidden[0]
+            hidden.zero_()  # the kernel leaves its own bytes behind
+
+        def counter(*a):
+            call(*a)
+            calls[0] += 1
+            bufs["b8_out"][0, 1, 0, 2] = float(calls[0])
+        return {"block5": stale, "block8": counter}.get(step, call)
+    picks, wk = _poisoned_walk(wrong)
+    with pytest.raises(PB.PlanCheckError) as err:
+        wk.walk()
+    print(err.value)
+    fails = err.value.failures
+    p5 = [m for b, v, m in fails if (b, v) == ("b5_out", picks["block5"])]
+    assert len(p5) == 1 and "the poisoned run differs: P != A at 1 of" in p5[0] and p5[0].endswith("first at (1, 2, 3, 4)")
+    p8 = [m for b, v, m in fails if (b, v) == ("b8_out", picks["block8"])]
+    assert p8 and "not reproducible: A' != A at 1 of" in p8[0] and p8[0].endswith("first at (0, 1, 0, 2)")
+    assert {b for b, _, _ in fails} == {"b5_out", "b8_out"}
 
 
 def test_variant_without_a_family_is_an_error(no_gpu):

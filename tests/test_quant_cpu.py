@@ -311,3 +311,66 @@ def test_plan_walker_sees_logits_padding_and_label_errors(exact_plan):
             I.check_plan(hm, ops, bufs, frames, lx, ly, run=False, select=lambda n: n == "labels")
     finally:
         bufs["labels"].copy_(lab)
+
+
+def _poisoned_walk(exact_plan, wrong):
+    """``check_plan(chip_poison=...)`` over the projection and the logits of the exact plan with
+    host ops (``int8_ref.reference_ops``), ``wrong(name, write, hidden, calls)`` wrapping the
+    picked op of each. The poison callable NaN-fills ``hidden``, the stand-in for on-chip state."""
+    hm, ops, bufs, frames, lx, ly = exact_plan
+    sel = lambda n: n in ("aspp_proj", "logits")  # noqa: E731
+    hops = I.reference_ops(hm, ops, bufs, frames, lx, ly, only=sel)
+    hidden, calls = torch.zeros(1), [0]
+    for op, (_, name, _) in zip(hops, I.plan_steps(hm)):
+        if sel(name):
+            vname, (write,) = op.variants[op.pick]
+            op.variants[op.pick] = (vname, [wrong(name, write, hidden, calls)])
+    saved = {n: bufs[n].clone() for n in ("aspp_proj", "logits")}
+    try:
+        return I.check_plan(hm, hops, bufs, frames, lx, ly, run=True, every_variant=False, select=sel,
+                            chip_poison=lambda: hidden.fill_(float("nan")))
+    finally:
+        for n, t in saved.items():
+            bufs[n].copy_(t)
+
+
+def test_poisoned_walk_passes_on_clean_ops(exact_plan):
+    rep = _poisoned_walk(exact_plan, lambda name, write, hidden, calls: write)
+    assert [r[0] for r in rep] == ["aspp_proj", "logits"]
+
+
+def test_poisoned_walk_sees_stale_state_and_a_call_counter(exact_plan):
+    """An op that adds a hidden host tensor (NaN once poisoned, cleared by the op as a kernel
+    overwrites its LDS) is reported as P != A at its buffer and variant; one that adds its call
+    count as not reproducible."""
+    hm, ops = exact_plan[:2]
+    pick = {op.name: op.variants[op.pick][0] for op in ops if hasattr(op, "variants")}
+    names = {name: op.name for op, (_, name, _) in zip(ops, I.plan_steps(hm)) if hasattr(op, "variants")}
+
+    def stale(name, write, hidden, calls):
+        def op(*a):
+            write(*a)
+            if name == "logits":
+                t = exact_plan[2][name]
+                t[0, 1, 2, 3] = t[0, 1, 2, 3].float() + hidden[0]
+            hidden.zero_()  # every kernel leaves its own bytes behind
+        return op
+    with pytest.raises(AssertionError) as err:
+        _poisoned_walk(exact_plan, stale)
+    lines = str(err.value).splitlines()[1:]
+    assert len(lines) == 1 and lines[0].startswith(f"logits/{pick[names['logits']]}: the poisoned run differs: P != A "
+                                                   "at 1 of ") and lines[0].endswith("first at (0, 1, 2, 3)"), lines
+
+    def counter(name, write, hidden, calls):
+        def op(*a):
+            write(*a)
+            if name == "aspp_proj":
+                calls[0] += 1
+                exact_plan[2][name][1, 0, 0, 0] = calls[0]
+        return op
+    with pytest.raises(AssertionError) as err:
+        _poisoned_walk(exact_plan, counter)
+    lines = str(err.value).splitlines()[1:]
+    assert any(ln.startswith(f"aspp_proj/{pick[names['aspp_proj']]}: not reproducible: A' != A at 1 of ") and
+               ln.endswith("first at (1, 0, 0, 0)") for ln in lines), lines
+    assert all(ln.startswith("aspp_proj/") for ln in lines), lines
