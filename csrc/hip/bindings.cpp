@@ -579,6 +579,20 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("stream"));
   m.attr("LABEL_STABLE_CHUNK") = label_stable_chunk();
 
+  m.def("label_smooth",
+        [](uintptr_t labels_in, uintptr_t labels_out, uintptr_t conf_in, uintptr_t conf_out, int B,
+           int H, int W, int crop_h, int crop_w, int R, uintptr_t stream) {
+          LabelSmoothParams p;
+          p.labels_in = P<const uint8_t>(labels_in); p.labels_out = P<uint8_t>(labels_out);
+          p.conf_in = P<const uint8_t>(conf_in); p.conf_out = P<uint8_t>(conf_out);
+          p.B = B; p.H = H; p.W = W; p.crop_h = crop_h; p.crop_w = crop_w; p.R = R;
+          label_smooth(p, S(stream));
+        },
+        py::arg("labels_in"), py::arg("labels_out"), py::arg("conf_in"), py::arg("conf_out"),
+        py::arg("B"), py::arg("H"), py::arg("W"), py::arg("crop_h"), py::arg("crop_w"), py::arg("R"),
+        py::arg("stream"));
+  m.attr("LABEL_SMOOTH_TILE") = py::make_tuple(label_smooth_tile_w(), label_smooth_tile_h());
+
   m.def("yuv422_to_bgr",
         [](uintptr_t src, uintptr_t dst, unsigned long long n_macropixels, bool uyvy, uintptr_t stream) {
           yuv422_to_bgr(P<const uint8_t>(src), P<uint8_t>(dst), (size_t)n_macropixels, uyvy, S(stream));

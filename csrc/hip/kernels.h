@@ -510,4 +510,23 @@ size_t label_stable_state_bytes(int streams, int crop_h, int crop_w);
 int label_stable_chunk();  // flat crop pixels per workgroup
 void label_stable(const LabelStableParams& p, hipStream_t s);
 
+// ---- spatial label smoothing (label_smooth.hip; the definition is postprocess/smooth.py) -------
+// Ahead of every other post-processing kernel on the same stream, label_stable included: every
+// crop pixel takes the most frequent label of its (2R+1) x (2R+1) window clipped to the crop (R
+// in 1 .. 3); the centre keeps its label when none has more votes, else the smallest label with
+// the most votes wins. With conf planes (both set or both null) an unchanged pixel keeps its
+// code, a changed one gets the floor mean of the winning voters' codes. Out of place only (the
+// outputs never alias the inputs); every byte of the outputs is written, pad pixels copied.
+// H * W < 2^31, B <= 65535.
+struct LabelSmoothParams {
+  const uint8_t* labels_in = nullptr;  // [B, H, W] (row stride W)
+  uint8_t* labels_out = nullptr;
+  const uint8_t* conf_in = nullptr;    // [B, H, W] or null
+  uint8_t* conf_out = nullptr;
+  int B = 0, H = 0, W = 0, crop_h = 0, crop_w = 0, R = 0;
+};
+int label_smooth_tile_w();  // the pixels of a workgroup's tile
+int label_smooth_tile_h();
+void label_smooth(const LabelSmoothParams& p, hipStream_t s);
+
 }  // namespace ssa

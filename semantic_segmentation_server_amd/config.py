@@ -79,6 +79,7 @@ class Config:
     event_log: int = 4096                  # events kept per stream for GetZoneEvents (at least max_events)
     stable_labels: int = 0                 # hold each pixel's label until another is seen N frames in a row (0: off; 2 .. 255)
     stable_min_confidence: float = 0.0     # ignore observations below this confidence, in [0, 1] (0: no gate)
+    smooth_labels: int = 0                 # majority label of each pixel's (2R+1)^2 window, ahead of stable_labels (0: off; 1 .. 3)
     # --- distributed ---
     gpus: int = 1
     ingest: str = "local"                  # local (per-rank H2D) | scatter (rank-0 RCCL scatter)
@@ -136,6 +137,8 @@ class Config:
         if float(self.stable_min_confidence) > 0.0 and not self.serve_confidence:
             raise ValueError(f"--stable_min_confidence {self.stable_min_confidence} requires "
                              "--serve_confidence: the gate reads the per-pixel confidence plane")
+        if not 0 <= int(self.smooth_labels) <= 3:
+            raise ValueError(f"--smooth_labels {self.smooth_labels} outside 1 .. 3 (0: off)")
         if self.pixel_format != "bgr":
             if self.camera_width % 2:
                 raise ValueError(f"--pixel_format {self.pixel_format} packs pixels in pairs: "
@@ -269,6 +272,11 @@ def add_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--stable_min_confidence", type=float, default=d.stable_min_confidence,
                    help="with --stable_labels: ignore an observation whose confidence is below "
                         "this (0 .. 1; 0: no gate); requires --serve_confidence")
+    p.add_argument("--smooth_labels", type=int, default=d.smooth_labels, metavar="R",
+                   help="replace each pixel's label by the most frequent label of its (2R+1) x (2R+1) "
+                        "window (1 .. 3), on the device ahead of --stable_labels and all "
+                        "post-processing; records, masks, regions, tracks, zones and presence see "
+                        "the smoothed maps (0: off)")
     p.add_argument("--gpus", type=int, default=d.gpus)
     p.add_argument("--ingest", choices=["local", "scatter"], default=d.ingest)
     p.add_argument("--gather", choices=["auto", "rccl", "host"], default=d.gather,

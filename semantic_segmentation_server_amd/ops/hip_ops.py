@@ -1711,6 +1711,56 @@ def label_stable(labels_in, labels_out, conf_in, conf_out, state, tables, *, cou
     return labels_out
 
 
+def label_smooth_tile():
+    """(width, height) of a workgroup's tile of ``label_smooth`` (the module's LABEL_SMOOTH_TILE)."""
+    tw, th = _hip_mod().LABEL_SMOOTH_TILE
+    return int(tw), int(th)
+
+
+def label_smooth(labels_in, labels_out, conf_in, conf_out, *, B, H, W, crop_h, crop_w, R):
+    """Spatial label smoothing on the current stream (csrc/hip/label_smooth.hip;
+    postprocess/smooth.py is the definition): every pixel of ``labels_in[:, :crop_h, :crop_w]``
+    takes the most frequent label of its (2R+1) x (2R+1) window clipped to the crop; the centre
+    keeps its label when none has more votes, else the smallest label with the most votes wins.
+    With the conf planes an unchanged pixel keeps its code and a changed one gets the floor mean
+    of the winning voters' codes. Out of place only: no plane may alias or overlap another, and
+    every byte of the outputs is written (pad pixels are copied). ``conf_in`` / ``conf_out``:
+    both uint8 [B, H, W] or both None."""
+    B, H, W, crop_h, crop_w, R = (int(v) for v in (B, H, W, crop_h, crop_w, R))
+    if (conf_in is None) != (conf_out is None):
+        raise ValueError("label_smooth: conf_in and conf_out are both given or both None")
+    if not 1 <= B <= 65535:
+        raise ValueError(f"label_smooth: B {B} outside 1 .. 65535")
+    for t, name in ((labels_in, "labels_in"), (labels_out, "labels_out"), (conf_in, "conf_in"),
+                    (conf_out, "conf_out")):
+        if t is None:
+            continue
+        _chk(t, torch.uint8, name)
+        if tuple(t.shape) != (B, H, W):
+            raise ValueError(f"{name}: shape {tuple(t.shape)} != ({B}, {H}, {W})")
+    if H * W >= 1 << 31:
+        raise ValueError(f"label_smooth: {H} x {W} pixels, a plane has fewer than 2^31")
+    if not (1 <= crop_h <= H and 1 <= crop_w <= W):
+        raise ValueError(f"label_smooth: crop {crop_h} x {crop_w} outside the {H} x {W} map")
+    if not 1 <= R <= 3:
+        raise ValueError(f"label_smooth: R {R} outside 1 .. 3")
+    planes = [(t, name) for t, name in ((labels_in, "labels_in"), (labels_out, "labels_out"),
+                                        (conf_in, "conf_in"), (conf_out, "conf_out")) if t is not None]
+    for t, name in planes[1:]:
+        if t.device != labels_in.device:
+            raise ValueError(f"label_smooth: {name} is on another device than labels_in")
+    nbytes = B * H * W
+    for i, (a, na) in enumerate(planes):  # a stencil cannot run in place: nothing may alias
+        for b, nb in planes[i + 1:]:
+            pa, pb = a.data_ptr(), b.data_ptr()
+            if pa < pb + nbytes and pb < pa + nbytes:
+                raise ValueError(f"label_smooth: {na} and {nb} overlap (the filter runs out of place)")
+    _hip_mod().label_smooth(_ptr(labels_in), _ptr(labels_out), _ptr(conf_in), _ptr(conf_out), B, H, W,
+                            crop_h, crop_w, R, _stream())
+    _dbg('label_smooth')
+    return labels_out
+
+
 def poison_chip(lds: bool = True, regs: bool = True, pat: int = 0x7FC07FC0) -> None:
     """Debug (scripts/debug_poison.py): fill every CU's LDS and every SIMD's register
     file with a NaN pattern, so the next kernel sees poison wherever it reads on-chip

@@ -24,8 +24,19 @@ class DevicePostprocess:
                  track_streams: int = 0, track_q: int = 0, zone_rows: int = 0, zone_classes: int = 0,
                  zone_conf: bool = False, presence_rows: int = 0, presence_q: int = 0,
                  stable_frames: int = 0, stable_gate: int = 0, stable_streams: int = 0,
-                 event_cap: int = 0):
+                 event_cap: int = 0, smooth_radius: int = 0):
         self.device = device
+        # smooth_radius (--smooth_labels): R of the windowed majority filter (label_smooth.hip),
+        # the first launch of run(), ahead of the stabilisation: out of place into a scratch
+        # plane per batch size (and a scratch code plane when a confidence plane is passed),
+        # from which the stabilisation writes the caller's planes, or a copy on the same stream
+        # without it -- either way the caller's planes hold the cleaned maps and every later
+        # kernel reads those. Stateless. 0: no kernel, no buffer, no launch
+        self.smooth_radius = int(smooth_radius)
+        if self.smooth_radius:
+            from . import smooth as SM
+            SM.check_params(self.smooth_radius)
+        self._smooth_bufs: Dict[tuple, tuple] = {}
         # event_cap (--serve_events): E of the zone-event kernels (zone_events.hip), the events
         # stored per frame; 0: no kernel, no buffer, no launch. They end the chain, read the
         # presence rows of the run and the track layout, and carry per stream its last presence
@@ -199,6 +210,15 @@ class DevicePostprocess:
         from ..runtime.feeder import split_batch
         return split_batch(B, self.track_streams or self.stable_streams)
 
+    def smooth_buffers(self, B: int, conf: bool):
+        """(scratch label plane, scratch code plane or None) of the label smoothing for a batch
+        of B frames: static like the records buffer. Every run writes every byte."""
+        key = (B, bool(conf))
+        if key not in self._smooth_bufs:
+            lab = torch.zeros((B, self.H, self.W), dtype=torch.uint8, device=self.device)
+            self._smooth_bufs[key] = (lab, torch.zeros_like(lab) if conf else None)
+        return self._smooth_bufs[key]
+
     def stable_buffers(self, B: int, crop_w: int, crop_h: int):
         """(layout table, the streams' carried state) of the label stabilisation; the state
         belongs to the crop alone, like the track state."""
@@ -304,15 +324,27 @@ class DevicePostprocess:
         the buffer written. With ``stable_frames`` the label stabilisation comes first, on the same stream
         (the graph stays a chain): ``labels`` -- and ``conf``, when passed -- are overwritten in
         place with the stabilised planes, which everything above then reads; the frames are the
-        next ones of their streams, laid out by ``track_counts``."""
+        next ones of their streams, laid out by ``track_counts``. With ``smooth_radius`` the label
+        smoothing comes before that, out of place into ``smooth_buffers(B)``; the stabilisation
+        then reads those planes, and without it they are copied back on the same stream: when
+        ``run`` returns, ``labels`` and ``conf`` hold the smoothed (and stabilised) maps."""
         B = labels.shape[0]
         if labels.shape[1:] != (self.H, self.W):
             raise ValueError(f"labels {tuple(labels.shape)} != (B, {self.H}, {self.W})")
+        if self.stable_frames and self.stable_gate and conf is None:
+            raise ValueError("DevicePostprocess.run: stable_gate needs the conf plane")
+        raw, raw_conf = labels, conf  # what the stabilisation reads
+        if self.smooth_radius:
+            raw, raw_conf = self.smooth_buffers(B, conf is not None)
+            hip_ops.label_smooth(labels, raw, conf, raw_conf, B=B, H=self.H, W=self.W, crop_h=crop_h,
+                                 crop_w=crop_w, R=self.smooth_radius)
+            if not self.stable_frames:  # device to device, same stream: the graph stays a chain
+                labels.copy_(raw)
+                if conf is not None:
+                    conf.copy_(raw_conf)
         if self.stable_frames:
-            if self.stable_gate and conf is None:
-                raise ValueError("DevicePostprocess.run: stable_gate needs the conf plane")
             tables, state = self.stable_buffers(B, crop_w, crop_h)
-            hip_ops.label_stable(labels, labels, conf, conf, state, tables,
+            hip_ops.label_stable(raw, labels, raw_conf, conf, state, tables,
                                  counts=self.track_counts(B), B=B, H=self.H, W=self.W,
                                  crop_h=crop_h, crop_w=crop_w, N=self.stable_frames,
                                  g=self.stable_gate)

@@ -9,7 +9,9 @@ written by the last kernels of the post-processing chain (their dwell state live
 track state), or None; ``events``: --serve_events event words, written by the kernels that then
 end the chain, or None). With --stable_labels the first launch of the post-processing chain
 rewrites ``labels`` (and ``conf``) in place with the stabilised planes, whose per-stream state
-lives there too: after the post-processing they are what the step hands out.
+lives there too: after the post-processing they are what the step hands out. With
+--smooth_labels the spatial filter is launched before that, into scratch planes of the
+DevicePostprocess, and the same holds: ``labels`` (and ``conf``) end up smoothed.
 ``replay()`` issues that form's replays, waits and event records; after ``consumed`` the buffer
 may be refilled (None: the model ran on the caller's stream).
 

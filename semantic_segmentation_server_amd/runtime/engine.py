@@ -233,6 +233,14 @@ class Engine:
             SB.check_params(self.stable_frames, self.stable_gate, self.serve_confidence)
             self.stable_streams = max(1, int(cfg.streams))
             self._stabilizers = SB.Stabilizers(self.stable_frames, self.stable_gate)
+        # --smooth_labels R: every pixel takes the most frequent label of its (2R+1)^2 window
+        # (postprocess/smooth.py), ahead of the stabilisation and all post-processing: the label
+        # maps (and the confidence plane) of a step ARE the smoothed ones. Stateless per frame,
+        # so every capture form and every stream layout runs it. 0: off -- no kernel, no buffer
+        self.smooth_radius = int(getattr(cfg, "smooth_labels", 0) or 0)
+        if self.smooth_radius:
+            from ..postprocess import smooth as SM
+            SM.check_params(self.smooth_radius)
         # --pixel_format yuyv | uyvy: frames arrive as packed 4:2:2 bytes, (B, Hc, Wc, 2), and
         # are converted to BGR ahead of the model (to_bgr). bgr: no kernel, no buffer
         self.pixel_format = cfg.pixel_format
@@ -392,7 +400,9 @@ class Engine:
                                                stable_frames=self.stable_frames,
                                                stable_gate=self.stable_gate,
                                                stable_streams=self.stable_streams,
-                                               **({"event_cap": self.event_cap} if self.event_cap else {}))
+                                               **({"event_cap": self.event_cap} if self.event_cap else {}),
+                                               **({"smooth_radius": self.smooth_radius}
+                                                  if self.smooth_radius else {}))
             if self.zone_rows > 1:
                 self._hip_post.set_zone_plane(self.zone_plane)
         kw = {"zone_out": zone_out} if self.zone_rows else {}
@@ -474,6 +484,18 @@ class Engine:
             self._events.reset()
         if self._hip_post is not None:
             self._hip_post.reset_tracks()
+
+    def host_smooth(self, labels: torch.Tensor, conf: Optional[torch.Tensor]):
+        """``smooth_radius`` on the host paths (the CPU, and a GPU without device
+        post-processing), ahead of ``host_stable``: ``labels`` (and ``conf``) are overwritten in
+        place with the smoothed planes (postprocess/smooth.py), which are also returned."""
+        from ..postprocess import smooth as SM
+        lab, cf = SM.apply(labels.cpu().numpy(), None if conf is None else conf.cpu().numpy(),
+                           self.crop_w, self.crop_h, self.smooth_radius)
+        labels.copy_(torch.from_numpy(lab))
+        if conf is not None:
+            conf.copy_(torch.from_numpy(cf))
+        return labels, conf
 
     def host_stable(self, labels: torch.Tensor, conf: Optional[torch.Tensor], streams=None):
         """``stable_frames`` on the host paths (the CPU, and a GPU without device
@@ -585,7 +607,9 @@ class Engine:
         # no device post-processing: on the CPU the masks are encoded here; a GPU's host
         # post-processing path encodes them where it brings the label maps to the host
         host = not self.is_cuda
-        if host and self.stable_frames:  # a GPU's host path: run_device, once the maps exist
+        if host and self.smooth_radius:  # a GPU's host path: run_device, once the maps exist
+            labels, conf = self.host_smooth(labels, conf)
+        if host and self.stable_frames:  # the same
             labels, conf = self.host_stable(labels, conf)
         mask = torch.from_numpy(self.host_masks(labels).view(np.int32)) if host and self.mask_cap else None
         regions = torch.from_numpy(self.host_regions(labels, conf).view(np.int32)) \
@@ -749,13 +773,17 @@ class Engine:
         return self._gpu_host_stable(step.labels), step.post
 
     def _gpu_host_stable(self, labels: torch.Tensor) -> torch.Tensor:
-        """``stable_frames`` on a GPU without device post-processing: the label maps (and
-        ``conf_plane``) of the step just issued are stabilised on the host and written back in
-        place, once the stream has produced them; every consumer then reads those. Anything
-        else: ``labels`` as they are (the device chain has stabilised them already)."""
-        if self.stable_frames and self.is_cuda and not self._use_device_post():
+        """``smooth_radius`` and ``stable_frames`` on a GPU without device post-processing: the
+        label maps (and ``conf_plane``) of the step just issued are smoothed, then stabilised, on
+        the host and written back in place, once the stream has produced them; every consumer
+        then reads those. Anything else: ``labels`` as they are (the device chain has cleaned
+        them already)."""
+        if (self.smooth_radius or self.stable_frames) and self.is_cuda and not self._use_device_post():
             torch.cuda.current_stream(self.device).synchronize()
-            self.host_stable(labels, self.conf_plane)
+            if self.smooth_radius:
+                self.host_smooth(labels, self.conf_plane)
+            if self.stable_frames:
+                self.host_stable(labels, self.conf_plane)
         return labels
 
     # ------------------------------------------------------------ post/host
@@ -805,6 +833,8 @@ class Engine:
             frames = torch.from_numpy(np.ascontiguousarray(frames_host))
             with torch.no_grad():
                 labels, self.conf_plane = self._infer(frames)
+            if self.smooth_radius:
+                labels, self.conf_plane = self.host_smooth(labels, self.conf_plane)
             if self.stable_frames:
                 labels, self.conf_plane = self.host_stable(labels, self.conf_plane,
                                                            _per_frame(streams, len(frame_ids)))
